@@ -9,7 +9,7 @@ vocab back in host memory.  OWT itself is not available offline; the corpus is t
 deterministic generator (bpe_synth_corpus_host), written once to a scratch file before timing.
 
 `value` is that end-to-end rate ("input MB/s = N / end-to-end wall, file read ->
-merges in host memory").  `device_resident` is the same training with the corpus already in HBM
+merges in host memory").  `device_resident` (--full) is the same training with the corpus already in HBM
 (train_bpe_device), i.e. without the file read and the host->device copy.
 
 GPUs (strong scaling: the corpus size is fixed, --bytes in total):
@@ -21,11 +21,19 @@ GPUs (strong scaling: the corpus size is fixed, --bytes in total):
     WORLD_SIZE.
 `n_gpus` reports the ranks that actually took part (from the library's stats).
 
-Prints ONE JSON line on rank 0.  Extra fields: merges_per_s, merge_loop (trips, time per trip),
-encode (Tokenizer.encode of the corpus with the trained merges, device to device), roofline of
-the dominant kernel (HIP events stamped by the kernel's own dispatch, on the library's stream),
-and cpu_baseline: the pure-Python port of the reference (oracle/cpu_ref.py) on a bounded sample,
-timed on this host (rank 0, N = 1 only).
+Prints ONE JSON line on rank 0.  A plain run (`python bench.py --gpus 1 --steps N --warmup W`)
+writes the corpus file, warms up, times the N steps and prints the line: value, ms_per_step,
+merges_per_s, merge_loop (trips, time per trip) and the roofline of the dominant kernel (HIP
+events stamped by the kernel's own dispatch, on the library's stream), all from the timed steps.
+`--dump-outputs DIR` also writes the last timed step's vocab and merges as DIR/<name>.npy
+(dump_outputs); the corpus depends only on --bytes, --seed and --flavour, so two builds can be
+compared array for array.
+
+`--full` adds the side legs, each a run of its own after the timed steps: device_resident, encode
+(Tokenizer.encode of the corpus with the trained merges, device to device, and encode_file end to
+end), parity (the result against the committed scale golden) and cpu_baseline: the pure-Python
+port of the reference (oracle/cpu_ref.py) on a bounded sample, timed on this host (rank 0, N = 1
+only).  Without --full these fields are null.
 """
 from __future__ import annotations
 
@@ -60,6 +68,11 @@ def parse():
     ap.add_argument("--flavour", type=int, default=0, help="0 OWT-like, 1 TinyStories-like")
     ap.add_argument("--corpus-dir", default=os.environ.get("BPE355_BENCH_DIR", tempfile.gettempdir()))
     ap.add_argument("--keep-corpus", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side legs: device_resident, encode, cpu_baseline "
+                         "and the parity check against the scale golden (each has its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result (vocab and merges) as DIR/<name>.npy")
     ap.add_argument("--no-device-resident", action="store_true")
     ap.add_argument("--no-encode", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -75,7 +88,33 @@ def parse():
     ap.add_argument("--no-file", action="store_true",
                     help="profiling runs: skip the file path (every k_count2 launch then covers the whole "
                          "corpus); the line then reports the HBM-resident rate")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run times its steps and nothing else; with --no-file the HBM-resident training
+        # is the timed path itself, so that leg stays
+        args.no_encode = args.no_cpu_baseline = True
+        args.no_device_resident = args.no_device_resident or not args.no_file
+    return args
+
+
+def dump_outputs(out_dir, vocab, merges):
+    """The timed path's result as a caller receives it, (vocab: dict[int, bytes], merges:
+    list[tuple[bytes, bytes]]), flattened to float32 arrays (every value is a byte or a length, so
+    float32 holds it exactly): vocab_lens[i] = len(vocab[i]) and vocab_bytes = the tokens' bytes
+    in id order; merges_lens[r] = (len(a), len(b)) and merges_bytes = a + b of every merge in
+    order.  1.6 MB at vocab 32000."""
+    import numpy as np
+    d = pathlib.Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    toks = [vocab[i] for i in range(len(vocab))]
+    arrays = {
+        "vocab_lens": np.array([len(t) for t in toks], dtype=np.float32),
+        "vocab_bytes": np.frombuffer(b"".join(toks), dtype=np.uint8).astype(np.float32),
+        "merges_lens": np.array([(len(a), len(b)) for a, b in merges], dtype=np.float32).reshape(-1, 2),
+        "merges_bytes": np.frombuffer(b"".join(a + b for a, b in merges), dtype=np.uint8).astype(np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a)
 
 
 def write_corpus(L, path: pathlib.Path, n: int, seed: int, flavour: int):
@@ -380,6 +419,8 @@ def main():
             "count_aggregation": {"records": s0["n_count_records"], "batches": s0["n_count_batches"],
                                   "ms": round(s0["count_reduce_ms"], 2)}}
 
+    if args.dump_outputs and rank == 0:   # the last timed step's result
+        dump_outputs(args.dump_outputs, vocab, merges)
     ms_per_step = elapsed / args.steps * 1e3
     value = n / (elapsed / args.steps) / 1e6
     rounds = len(merges)
@@ -488,7 +529,8 @@ def main():
                        "corpus_bytes": n, "vocab_size": args.vocab, "merges": rounds,
                        "seed": args.seed, "flavour": args.flavour, "parallelism": par},
             # the timed steps' result against the committed scale golden of this corpus
-            "parity": golden_parity(n, args.seed, args.flavour, args.vocab, vocab, merges),
+            "parity": (golden_parity(n, args.seed, args.flavour, args.vocab, vocab, merges) if args.full else
+                       {"parity": None, "golden": None, "note": "not checked in this run: python bench.py --full"}),
             "merges_per_s": round(rounds / (avg["t_merge_ms"] / 1e3), 1) if avg["t_merge_ms"] else None,
             "device_resident": device_resident,
             "merge_loop": merge_loop,

@@ -8,7 +8,7 @@ for rep in ${REPS:-1 2}; do
   for spec in "$@"; do
     v=${spec%%:*}; envs=""; [ "$spec" != "$v" ] && envs=$(echo ${spec#*:} | tr ',' ' ')
     log=$OUT/$(echo $spec | tr ':,=' '___').$rep.log
-    env $envs BPE355_LIB=build/variants/$v/libbpe355.so timeout -k 10 200 python -u bench.py --steps 2 --warmup 1 --no-encode --no-cpu-baseline --no-timing > $log 2>&1 || { echo "$spec failed"; tail -5 $log; exit 1; }
+    env $envs BPE355_LIB=build/variants/$v/libbpe355.so timeout -k 10 200 python -u bench.py --full --steps 2 --warmup 1 --no-encode --no-cpu-baseline --no-timing > $log 2>&1 || { echo "$spec failed"; tail -5 $log; exit 1; }
     python - $log "$spec" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

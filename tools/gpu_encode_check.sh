@@ -8,7 +8,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_large.py tests/test_gpu_bul
 tail -1 $OUT/tests.log
 
 
-timeout -k 10 400 python -u bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -20 $OUT/bench.log; exit 1; }
+timeout -k 10 400 python -u bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -20 $OUT/bench.log; exit 1; }
 python3 -c "
 import json; d=json.loads(open('$OUT/bench.log').read().strip().splitlines()[-1]); e=d['encode']; print('value', d['value'], 'merge', d['phases_ms']['t_merge_ms'], 'device enc', e['value'], e['ids_rank0'], 'e2e', json.dumps(e['end_to_end']))"
 timeout -k 10 300 python -u tools/enc_file_bench.py > $OUT/encfile.log 2>&1 || { echo "encfile failed"; tail -20 $OUT/encfile.log; exit 1; }

@@ -14,7 +14,7 @@ timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/s
 tail -1 $OUT/smoke.log
 bash tools/gpu_pmc_all.sh $TAG/pmc || exit 1
 cp $OUT/pmc/traffic.json profiles/r03/traffic.json
-timeout -k 10 600 python -u bench.py --steps 10 --warmup 2 --keep-corpus > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -30 $OUT/bench.log; exit 1; }
+timeout -k 10 600 python -u bench.py --full --steps 10 --warmup 2 --keep-corpus > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -30 $OUT/bench.log; exit 1; }
 tail -1 $OUT/bench.log | cut -c1-300
 cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$OUT/prof -o run -- python3 -u $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-file --no-encode --steps 2 --warmup 1 --keep-corpus > $GRAFT_REPO_ROOT/$OUT/bench_prof.log 2>&1 || { echo "rocprof failed"; tail -30 $GRAFT_REPO_ROOT/$OUT/bench_prof.log; exit 1; }
 cd $GRAFT_REPO_ROOT
