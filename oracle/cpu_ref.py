@@ -32,11 +32,14 @@ def count_pretokens(text: str, specials) -> dict:
 
 
 def train(text: str, vocab_size: int, specials=(), deadline: float | None = None,
-          round_cap_s: float | None = None, progress: list | None = None, progress_every: int = 1000):
+          round_cap_s: float | None = None, progress: list | None = None, progress_every: int = 1000,
+          on_round=None):
     """Returns (vocab, merges, info).  info["complete"] is False if the deadline (absolute) or the
     cap on the merge rounds' wall time (from the end of the count) stopped it.  `progress`, when
     given, receives (rounds done, seconds since the start, live pairs) every `progress_every`
-    rounds (tools/cpu_port_full.py uses it to check the bench's flat-rate extrapolation)."""
+    rounds (tools/cpu_port_full.py uses it to check the bench's flat-rate extrapolation).
+    `on_round`, when given, is called as on_round(pairs, (a, b)) in every round with the pair
+    counts and the winner before the words are rewritten (tests/tie_cases.py reads the ties)."""
     t0 = time.perf_counter()
     vocab_list: list = []
     present = set()
@@ -77,6 +80,8 @@ def train(text: str, vocab_size: int, specials=(), deadline: float | None = None
         if deadline is not None and time.perf_counter() > deadline:
             break
         a, b = max(pairs, key=lambda p: (pairs[p], p))
+        if on_round is not None:
+            on_round(pairs, (a, b))
         new = a + b
         if new not in present:
             present.add(new)

@@ -9,6 +9,7 @@ import pytest
 
 import golden_cases as G
 import gpt2_files
+import tie_cases
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -116,6 +117,32 @@ def test_train_matches_oracle_tie_heavy(seed):
     vocab = rng.choice([300, 400, 1000])
     want = oracle.train_raw(data, vocab, ["<|endoftext|>"])
     got = bpe_amd.train_bpe_bytes(data, vocab, ["<|endoftext|>"])
+    assert got[1] == want[1]
+    assert got[0] == want[0]
+
+
+@pytest.mark.parametrize("knob", [None, "BPE355_BATCH=0", "BPE355_FOLD=1"])
+@pytest.mark.parametrize("kind,seed", tie_cases.all_cases())
+def test_train_matches_oracle_deep_ties(kind, seed, knob, monkeypatch):
+    """Ties decided past the zero-padded 8-byte prefix key (cand_better -> cmp_tok_tail: a byte at
+    index >= 8, or the length, "\\x00" against "\\x00\\x00"); tests/test_tie_cases.py shows on the
+    CPU that each case has such rounds.  Batched trips, the per-round kernels and the fused trip."""
+    if knob:
+        monkeypatch.setenv(*knob.split("="))
+    data = tie_cases.case(seed, kind).encode("utf-8")
+    want = oracle.train_raw(data, tie_cases.VOCAB, [])
+    got = bpe_amd.train_bpe_bytes(data, tie_cases.VOCAB, [])
+    assert got[1] == want[1]
+    assert got[0] == want[0]
+
+
+@pytest.mark.parametrize("kind", tie_cases.KINDS)
+def test_train_matches_oracle_deep_ties_scaled(kind):
+    """2000 words of the same stems, vocab 1200: a batched trip's ranking list holds several
+    deep-tied entries at once."""
+    data = tie_cases.case(0, kind, tie_cases.SCALED_WORDS).encode("utf-8")
+    want = oracle.train_raw(data, tie_cases.SCALED_VOCAB, [])
+    got = bpe_amd.train_bpe_bytes(data, tie_cases.SCALED_VOCAB, [])
     assert got[1] == want[1]
     assert got[0] == want[0]
 

@@ -3921,7 +3921,8 @@ void MergeLoop<TokT>::run() {
         std::fprintf(stderr, "[bpe355 check-marks] nonzero cells left after the clear: %llu (first: trip %llu member %llu "
                              "cell %llu); bitmap words left: %llu; apply workgroups with another view: %llu (first: "
                              "trip %llu workgroup %llu)\n", d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7]);
-        BPE_REQUIRE(d[0] == 0 && d[4] == 0, BPE_E_HIP, "cell marks: a delta outside the marked blocks");
+        BPE_REQUIRE(d[0] == 0 && d[4] == 0 && d[5] == 0, BPE_E_HIP,
+                    "cell marks: a delta outside the marked blocks, or apply workgroups that listed different blocks");
     }
     if (trip_log_ && !trip_log_->empty()) {   // kTI ints per trip (k > 0: the trips that ran)
         if (FILE* f = std::fopen(trip_log_path, "wb")) {
