@@ -215,6 +215,25 @@ int bpe_tok_encode_chunks(bpe_tokenizer* tok, const uint8_t* utf8, size_t n, con
                           size_t n_starts, uint32_t* ids_out, size_t cap, size_t* n_out);
 int bpe_tok_encode_chunks_device(bpe_tokenizer* tok, const uint8_t* d_utf8, size_t n, const uint64_t* starts,
                                  size_t n_starts, uint32_t* d_out, size_t* n_out, void* hip_stream);
+/* Batch encode: encode(doc) for every doc = text[doc_starts[i] : doc_starts[i+1]) (the last runs to
+ * n), the ids concatenated; id_offsets gets n_docs + 1 entries: doc i's ids are
+ * ids[id_offsets[i] : id_offsets[i+1]).  doc_starts[0] == 0, non-decreasing, <= n, else BPE_E_ARG
+ * (equal starts: an empty document).  Exactly separate encode() calls, as the chunked encode
+ * above; the offsets are exact where summing the ids' byte lengths is not (several byte strings
+ * may share an id, a pre-token equal to a special has no id).  cap >= n always suffices. */
+int bpe_tok_encode_batch(bpe_tokenizer* tok, const uint8_t* utf8, size_t n, const uint64_t* doc_starts,
+                         size_t n_docs, uint32_t* ids_out, size_t cap, size_t* n_out, uint64_t* id_offsets_out);
+/* same, device-resident text, ids (d_out holds >= n) and offsets (n_docs + 1); doc_starts in host memory */
+int bpe_tok_encode_batch_device(bpe_tokenizer* tok, const uint8_t* d_utf8, size_t n, const uint64_t* doc_starts,
+                                size_t n_docs, uint32_t* d_out, size_t* n_out, uint64_t* d_id_offsets,
+                                void* hip_stream);
+/* CSR ids (as the batch encode returns them) -> a dense [n_rows, row_len] matrix of int32
+ * (elem_bytes 4) or int64 (8) in d_out, and d_lengths[i] = min(L_i, row_len).  A row longer than
+ * row_len keeps its first ids (flags & 1: its last); a shorter one is filled with pad on the
+ * right (flags & 2: on the left).  All pointers device memory; returns once the matrix is written. */
+int bpe_ids_pack_rows_device(const uint32_t* d_ids, const uint64_t* d_offsets, size_t n_rows, size_t row_len,
+                             int64_t pad, int flags, int elem_bytes, void* d_out, int32_t* d_lengths,
+                             void* hip_stream);
 /* The reference's dataset encoder (encode.py:18-38) on one file: the file is read by the library's
  * pinned multi-threaded reader into HBM, decoded as open(path, "r", encoding="utf-8") reads it
  * (strict UTF-8, universal newlines), cut into chars_per_piece-character pieces (f.read(1024*1024)),

@@ -135,6 +135,94 @@ class Tokenizer:
         _lib.check(rc, "encode")
         return list(out[: n_out.value])
 
+    # ------------------------------------------------------------------ batch encode
+    # encode(t) for every t of a list in one launch sequence: the texts are joined, the library
+    # encodes the join with a cut at every document start (bpe_tok_encode_batch: each document is
+    # segmented and pre-tokenized on its own, so a seam never merges trailing whitespace, a
+    # contraction or the halves of a special token) and reports where each document's ids begin.
+    # These methods run on the current device whatever set_num_gpus / BPE355_GPUS says: spreading
+    # the documents of one batch over devices is left to the caller.
+    @staticmethod
+    def _join(texts):
+        import numpy as np
+        datas = [t.encode("utf-8") for t in texts]
+        starts = np.zeros(len(datas) + 1, dtype=np.uint64)
+        if datas:
+            np.cumsum(np.fromiter(map(len, datas), dtype=np.uint64, count=len(datas)), out=starts[1:])
+        return b"".join(datas), starts
+
+    def encode_batch_np(self, texts: List[str]):
+        """-> (ids np.uint32 [total], offsets np.int64 [len(texts) + 1]): encode(texts[i]) is
+        ids[offsets[i]:offsets[i + 1]].  One UTF-8 join, one library call, one copy back; on the
+        current device (set_num_gpus does not apply)."""
+        import numpy as np
+        texts = list(texts)
+        h = self._device()
+        data, starts = self._join(texts)
+        n, nd = len(data), len(texts)
+        ids = np.empty(max(n, 1), dtype=np.uint32)
+        offsets = np.zeros(nd + 1, dtype=np.uint64)
+        n_out = ctypes.c_size_t(0)
+        if nd:
+            rc = _lib.lib().bpe_tok_encode_batch(h, data, n, starts.ctypes.data, nd, ids.ctypes.data, ids.size,
+                                                 ctypes.byref(n_out), offsets.ctypes.data)
+            _lib.check(rc, "encode_batch")
+        return ids[:n_out.value].copy(), offsets.astype(np.int64)
+
+    def encode_batch(self, texts: List[str]) -> List[List[int]]:
+        """[encode(t) for t in texts] in one library call (see encode_batch_np); on the current
+        device (set_num_gpus does not apply)."""
+        ids, offsets = self.encode_batch_np(texts)
+        flat, off = ids.tolist(), offsets.tolist()
+        return [flat[a:b] for a, b in zip(off, off[1:])]
+
+    def encode_batch_padded(self, texts: List[str], max_length: int | None = None, *, pad_id: int,
+                            truncation: str = "right", padding_side: str = "right", dtype=None):
+        """-> (tensor [len(texts), T] of dtype (torch.int64, or torch.int32) on the current device,
+        int32 lengths [len(texts)]).  T is max_length, or the longest row when it is None.  A row
+        longer than T loses ids on the `truncation` side ("right": the first T are kept, "left":
+        the last T); a shorter one is filled with pad_id on `padding_side`.  lengths[i] =
+        min(len(encode(texts[i])), T).  The text goes to the device once, the ids never leave it
+        (bpe_tok_encode_batch_device, then bpe_ids_pack_rows_device); on the current device
+        (set_num_gpus does not apply)."""
+        import torch
+        dtype = torch.int64 if dtype is None else dtype
+        if truncation not in ("right", "left") or padding_side not in ("right", "left"):
+            raise ValueError("truncation and padding_side are 'right' or 'left'")
+        if dtype not in (torch.int32, torch.int64):
+            raise ValueError("dtype is torch.int32 or torch.int64")
+        if max_length is not None and max_length < 0:
+            raise ValueError("max_length is negative")
+        texts = list(texts)
+        h = self._device()
+        L = _lib.lib()
+        data, starts = self._join(texts)
+        n, nd = len(data), len(texts)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        lengths = torch.zeros(nd, dtype=torch.int32, device=dev)
+        if nd == 0:
+            return torch.empty((0, max_length or 0), dtype=dtype, device=dev), lengths
+        stream = torch.cuda.current_stream()
+        sp = ctypes.c_void_p(stream.cuda_stream)
+        d_ids = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        d_off = torch.zeros(nd + 1, dtype=torch.int64, device=dev)
+        if n:
+            d_text = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
+            stream.synchronize()
+            n_out = ctypes.c_size_t(0)
+            _lib.check(L.bpe_tok_encode_batch_device(h, ctypes.c_void_p(d_text.data_ptr()), n, starts.ctypes.data, nd,
+                                                     ctypes.c_void_p(d_ids.data_ptr()), ctypes.byref(n_out),
+                                                     ctypes.c_void_p(d_off.data_ptr()), sp), "encode_batch")
+        T = int((d_off[1:] - d_off[:-1]).max()) if max_length is None else int(max_length)
+        out = torch.empty((nd, T), dtype=dtype, device=dev)
+        flags = (1 if truncation == "left" else 0) | (2 if padding_side == "left" else 0)
+        stream.synchronize()
+        _lib.check(L.bpe_ids_pack_rows_device(ctypes.c_void_p(d_ids.data_ptr()), ctypes.c_void_p(d_off.data_ptr()), nd,
+                                              T, int(pad_id), flags, 4 if dtype == torch.int32 else 8,
+                                              ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(lengths.data_ptr()),
+                                              sp), "pack rows")
+        return out, lengths
+
     def encode_iterable(self, iterable: Iterable[str]) -> Iterator[int]:
         """tokenizer.py:140-150: concatenate items until >= 2 MiB characters, encode each chunk."""
         it = iter(iterable)

@@ -24,6 +24,10 @@
 //      table words' slots -> their ids' info.
 //   5. k_enc_emit<count>, an exclusive scan of the chunks' id counts, k_enc_emit<write>: per
 //      chunk, ids assembled in LDS and stored with coalesced writes.
+//   5'. (encode_batch) the scan also notes, per document start, the record of the token that
+//      starts there; k_enc_cut_offsets turns those into id offsets with one more pass over the
+//      records, k_enc_doc_offsets hands every document its own.
+//   6. k_pack_rows: ids and offsets -> padded rows.
 
 #include <algorithm>
 #include <cmath>
@@ -491,6 +495,14 @@ struct ScanArgs {
     unsigned* status;
 };
 
+// The optional export of the scan (encode_batch): for every cut -- a document start inside the
+// text -- the index, inside its chunk's record run, of the token that starts there.
+struct ScanCuts {
+    const unsigned long long* cuts;   // sorted, distinct, in (0, n)
+    const uint32_t* chunk_cut0;       // n_chunks + 1: the first cut at or after each chunk's first byte
+    uint32_t* cut_rec;                // per cut: record index inside its chunk's run
+};
+
 // A workgroup appends its pending entries to a block of the pool it holds; a block is
 // chunk-sized (a chunk has at most one pre-token per byte), so a chunk that does not fit the
 // rest of the block takes a new one before its token phase and the appends never check.
@@ -521,8 +533,10 @@ __device__ __forceinline__ uint32_t dict_rec(uint32_t rec, size_t cap) {
 #ifndef BPE355_ENC_EARLY_PREFETCH
 #define BPE355_ENC_EARLY_PREFETCH 0
 #endif
-template <bool kAligned>
-__global__ void __launch_bounds__(256, BPE355_ENC_SCAN_WG) k_enc_scan4(ScanArgs A, EncDict D) {
+// kCuts: the instantiations of encode_batch also export every cut's record index (ScanCuts); in the
+// others C is never read.
+template <bool kAligned, bool kCuts>
+__global__ void __launch_bounds__(256, BPE355_ENC_SCAN_WG) k_enc_scan4(ScanArgs A, EncDict D, ScanCuts C) {
     __shared__ uint64_t s_mask[kWords];
     __shared__ unsigned long long c_key[kEncCache];
     __shared__ uint64_t c_lo[kEncCache], c_hi[kEncCache];
@@ -694,6 +708,20 @@ __global__ void __launch_bounds__(256, BPE355_ENC_SCAN_WG) k_enc_scan4(ScanArgs 
         __syncthreads();
         uint32_t toff = x - cnt;
         for (int w = 0; w < wave; ++w) toff += s_wsum[w];
+        if (kCuts) {   // the cuts in this block: a token starts at each (a cut ends every segment)
+            uint32_t lo = C.chunk_cut0[c];
+            const uint32_t q1 = C.chunk_cut0[c + 1];
+            for (uint32_t hi = q1; lo < hi;) {   // the first cut at or after blk
+                const uint32_t mid = lo + ((hi - lo) >> 1);
+                if (C.cuts[mid] < blk) lo = mid + 1;
+                else hi = mid;
+            }
+            for (; lo < q1; ++lo) {
+                const unsigned long long d = C.cuts[lo] - blk;
+                if (d >= 64) break;
+                C.cut_rec[lo] = toff + (uint32_t)__popcll(starts & ((1ULL << d) - 1));
+            }
+        }
         if (tid == 0) {
             const uint32_t total = s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
             // the chunk's run in the workgroup's region; a new region (one global reservation per
@@ -1266,6 +1294,131 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) k
     }
 }
 
+// ------------------------------------------------------------------ 5'. id offsets of the cuts
+// encode_batch: where the ids of the token at each cut begin in the output.  The scan left every
+// cut's record index inside its chunk's run (ScanCuts::cut_rec, increasing with the cut); a cut's
+// id offset is coff[part] + the ids of the part's records before that one.  Shaped like the
+// emit's count pass: a workgroup takes the chunk parts that hold a cut (the split is the emit's,
+// r0 = mc * part / kEmitParts), reads the part's records in rounds of 256 * kEmitR (each thread
+// kEmitR consecutive records, their gathers issued together), leaves the exclusive prefix of
+// their id counts in LDS and lets every cut of the round pick its entry -- one pass over the
+// records however many cuts there are.  It reads the infos the write pass reads (rec_info with
+// the write pass's EmitArgs), so it runs after the coff scan in every BPE355_ENC_FINALIZE mode.
+constexpr uint32_t kCutRound = 256u * kEmitR;
+
+__global__ void __launch_bounds__(256) k_enc_cut_offsets(EmitArgs A, const uint32_t* __restrict__ chunk_cut0,
+                                                         const uint32_t* __restrict__ cut_rec,
+                                                         unsigned long long* __restrict__ cut_off) {
+    __shared__ uint32_t s_pre[kCutRound];
+    __shared__ uint32_t s_ws[4];
+    const int tid = threadIdx.x;
+    // the first cut of [lo, hi) whose record index is at or past x
+    auto first_at = [&](uint32_t lo, uint32_t hi, uint32_t x) -> uint32_t {
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (cut_rec[mid] < x) lo = mid + 1;
+            else hi = mid;
+        }
+        return lo;
+    };
+    for (size_t c = blockIdx.x; c < A.n_chunks * kEmitParts; c += gridDim.x) {   // c: a part
+        const size_t ch = c / kEmitParts;
+        const unsigned part = (unsigned)(c % kEmitParts);
+        const uint32_t q0 = chunk_cut0[ch], q1 = chunk_cut0[ch + 1];
+        if (q0 == q1) continue;   // no cut in this chunk (uniform over the workgroup)
+        const uint32_t mc = A.rec_n[ch];
+        const uint32_t r0 = (uint32_t)((unsigned long long)mc * part / kEmitParts);
+        const uint32_t m = (uint32_t)((unsigned long long)mc * (part + 1) / kEmitParts) - r0;
+        uint32_t j = first_at(q0, q1, r0);             // the part's cuts: [j, j1)
+        const uint32_t j1 = first_at(j, q1, r0 + m);
+        if (j == j1) continue;
+        const uint32_t* __restrict__ r = A.recs + A.rec_base[ch] + r0;
+        const unsigned long long P = A.coff[c];
+        uint32_t run = 0;   // ids of the rounds before this one
+        for (uint32_t b = 0; b < m && j < j1; b += kCutRound) {
+            const uint32_t lo = b + tid * kEmitR;
+            uint32_t nid[kEmitR];
+#pragma unroll
+            for (int i = 0; i < kEmitR; ++i) nid[i] = lo + i < m ? info_nids(rec_info(A, r[lo + i])) : 0u;
+            uint32_t sum = 0;
+#pragma unroll
+            for (int i = 0; i < kEmitR; ++i) sum += nid[i];
+            uint32_t T;
+            uint32_t o = block_excl_scan(sum, s_ws, &T);
+#pragma unroll
+            for (int i = 0; i < kEmitR; ++i) {
+                s_pre[tid * kEmitR + i] = o;
+                o += nid[i];
+            }
+            __syncthreads();
+            const uint32_t jn = first_at(j, j1, r0 + b + kCutRound);   // the round's cuts: [j, jn)
+            for (uint32_t q = j + tid; q < jn; q += 256) {
+                const uint32_t k = cut_rec[q] - r0 - b;   // < kCutRound: [j, jn) is this round's
+                cut_off[q] = P + run + s_pre[k < kCutRound ? k : kCutRound - 1];
+            }
+            j = jn;
+            run += T;
+            __syncthreads();   // s_pre is reused by the next round
+        }
+    }
+}
+
+// every document start's id offset: 0 for a start at byte 0, the id total for one at the text's
+// end (and the closing entry), else its cut's offset
+constexpr uint32_t kDocAtZero = 0xFFFFFFFFu, kDocAtEnd = 0xFFFFFFFEu;
+__global__ void k_enc_doc_offsets(const uint32_t* __restrict__ doc_cut, size_t n, const unsigned long long* __restrict__ cut_off,
+                                  const unsigned long long* __restrict__ coff, const unsigned long long* __restrict__ ctot,
+                                  size_t n_parts, unsigned long long* __restrict__ out) {
+    const unsigned long long total = coff[n_parts - 1] + ctot[n_parts - 1];
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        // doc_cut null: no empty document, so document i > 0 starts at cut i - 1
+        const uint32_t k = doc_cut ? doc_cut[i] : i == 0 ? kDocAtZero : i == n - 1 ? kDocAtEnd : (uint32_t)(i - 1);
+        out[i] = k == kDocAtZero ? 0ULL : k == kDocAtEnd ? total : cut_off[k];
+    }
+}
+
+// ------------------------------------------------------------------ 6. padded rows
+// CSR ids (u32 ids, u64 row offsets) -> a dense [n_rows, row_len] matrix of OutT (int32 / int64)
+// and the rows' kept lengths.  Flags as bpe_ids_pack_rows_device: a row longer than row_len keeps
+// its first ids, or with kPackKeepLast its last; a shorter one is padded on the right, or with
+// kPackPadLeft on the left.  A thread fills one 16-byte unit of the output (kVec: row_len is a
+// multiple of the unit and the matrix is 16-byte aligned, so a unit lies in one row) or one
+// element; consecutive threads write consecutive addresses and read consecutive ids.
+constexpr int kPackKeepLast = 1, kPackPadLeft = 2;
+
+template <class OutT, bool kVec>
+__global__ void __launch_bounds__(256) k_pack_rows(const uint32_t* __restrict__ ids, const unsigned long long* __restrict__ off,
+                                                   size_t n_rows, size_t row_len, OutT pad, int flags,
+                                                   OutT* __restrict__ out, int32_t* __restrict__ lengths) {
+    constexpr unsigned kPer = kVec ? 16 / sizeof(OutT) : 1;
+    const size_t stride = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (size_t i = t0; i < n_rows; i += stride) {
+        const unsigned long long L = off[i + 1] - off[i];
+        lengths[i] = (int32_t)(L < row_len ? L : row_len);
+    }
+    const size_t units = n_rows * row_len / kPer;
+    for (size_t u = t0; u < units; u += stride) {
+        const size_t e = u * kPer, row = e / row_len, col = e - row * row_len;
+        const unsigned long long a = off[row], L = off[row + 1] - a;
+        const size_t len = L < row_len ? (size_t)L : row_len;
+        const unsigned long long src = (flags & kPackKeepLast) ? a + L - len : a;   // the first id kept
+        const size_t c0 = (flags & kPackPadLeft) ? row_len - len : 0;               // its column
+        OutT v[kPer];
+#pragma unroll
+        for (unsigned k = 0; k < kPer; ++k) {
+            const size_t cc = col + k;
+            v[k] = cc >= c0 && cc < c0 + len ? (OutT)ids[src + (cc - c0)] : pad;
+        }
+        if (kVec) {
+            uint4 w;
+            __builtin_memcpy(&w, v, 16);
+            *reinterpret_cast<uint4*>(out + e) = w;
+        } else {
+            out[e] = v[0];
+        }
+    }
+}
+
 __device__ __forceinline__ uint2 rank_of(const EncTables& E, uint32_t a, uint32_t b) {
     const unsigned long long key = ((((unsigned long long)a) << 32) | b) + 1ULL;
     size_t s = mix64(key) & E.pm_mask;
@@ -1364,6 +1517,9 @@ struct bpe_tokenizer {
         bpe::DevBuf<uint8_t> tmp;
         bpe::DevBuf<uint16_t> ids16;
         bpe::DevBuf<uint8_t> text, text2;   // the bulk encoder's file bytes (and its newline-translated copy)
+        // encode_batch: per chunk its first cut, per cut its record index and id offset, per document its cut
+        bpe::DevBuf<uint32_t> chunk_cut0, cut_rec, doc_cut;
+        bpe::DevBuf<unsigned long long> cut_off;
     } sc;
     // construction inputs, to build the same tables for the other ranks of a multi-device encode
     // (bpe_tok_encode_gpus); those copies own their stream and record buffer
@@ -1612,13 +1768,25 @@ void build_tokenizer(bpe_tokenizer& T, const uint8_t* vb, size_t vn, const uint8
 // result that of separate encode() calls on the pieces between them, concatenated: a cut ends
 // every segment, and a special token may not straddle one (encode.py's 1 M-character chunks,
 // encode_iterable's 2 MiB batches).
+// `docs` (encode_batch; its starts are then the cuts): d_out of it gets the id offset of every
+// document start and, as entry n_docs, the id count.
+struct DocStarts {
+    const uint64_t* starts;        // host: non-decreasing, starts[0] == 0, <= n
+    size_t n_docs;
+    unsigned long long* d_out;     // device: n_docs + 1 entries
+};
+
 template <class OutT>
 size_t encode_device(bpe_tokenizer& T, const uint8_t* d_text, size_t n, OutT* d_out,
-                     hipStream_t s, const std::vector<unsigned long long>& cuts_in = {}) {
+                     hipStream_t s, const std::vector<unsigned long long>& cuts_in = {},
+                     const DocStarts* docs = nullptr) {
     if (n == 0) return 0;
     std::vector<unsigned long long> cuts;
     for (unsigned long long c : cuts_in)
         if (c > 0 && c < n && (cuts.empty() || c > cuts.back())) cuts.push_back(c);
+    const bool want_cuts = docs && !cuts.empty();   // (no cut: every start is at byte 0 or at the end)
+    if (docs) BPE_REQUIRE(cuts.size() < 0xFFFFFFF0ull, BPE_E_LIMIT, "too many documents for one encode");
+    bool cuts_up = false;   // S.cuts holds the cuts
     EncTables E = T.tables();
     // 1. segments: every special match (k_find_specials), sorted on the device by (position,
     // index) -- by position, longest first (T.specials is longest first) -- then built into the
@@ -1652,6 +1820,7 @@ size_t encode_device(bpe_tokenizer& T, const uint8_t* d_text, size_t n, OutT* d_
             const size_t nc = cuts.size();
             S.cuts.reserve(std::max<size_t>(nc, 1));
             if (nc) to_device(S.cuts.p, cuts.data(), nc * 8, s);
+            cuts_up = true;
             // the matches no cut splits, in order (into sp_key)
             S.sp_flag.reserve(cnt32);
             S.sp_off.reserve(2);
@@ -1721,7 +1890,8 @@ size_t encode_device(bpe_tokenizer& T, const uint8_t* d_text, size_t n, OutT* d_
     const size_t n_chunks = (n + kChunk - 1) / kChunk;
     BPE_REQUIRE(n_chunks < (1ull << 32), BPE_E_LIMIT, "text too long for one encode");
     const bool aligned = (reinterpret_cast<uintptr_t>(d_text) & 15u) == 0;
-    auto kern = aligned ? k_enc_scan4<true> : k_enc_scan4<false>;
+    auto kern = want_cuts ? (aligned ? k_enc_scan4<true, true> : k_enc_scan4<false, true>)
+                          : (aligned ? k_enc_scan4<true, false> : k_enc_scan4<false, false>);
     int per_cu = 0, dev = 0, n_cu = 0;
     BPE_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, kStage));
     BPE_HIP(hipGetDevice(&dev));
@@ -1769,6 +1939,25 @@ size_t encode_device(bpe_tokenizer& T, const uint8_t* d_text, size_t n, OutT* d_
     S.block_used.reserve(std::max(pend_blocks, 1u));
     S.pend_nblk.reserve(1);
     const EncDict D = T.dict();
+    ScanCuts SC{nullptr, nullptr, nullptr};
+    if (want_cuts) {   // the cuts on the device, and every chunk's first one
+        const size_t nc = cuts.size();
+        if (!cuts_up) {
+            S.cuts.reserve(nc);
+            to_device(S.cuts.p, cuts.data(), nc * 8, s);
+        }
+        std::vector<uint32_t> first(n_chunks + 1);
+        size_t j = 0;
+        for (size_t c = 0; c <= n_chunks; ++c) {
+            while (j < nc && cuts[j] < (unsigned long long)c * kChunk) ++j;
+            first[c] = (uint32_t)j;
+        }
+        S.chunk_cut0.reserve(n_chunks + 1);
+        to_device(S.chunk_cut0.p, first.data(), (n_chunks + 1) * 4, s);
+        S.cut_rec.reserve(nc);
+        S.cut_off.reserve(nc);
+        SC = ScanCuts{S.cuts.p, S.chunk_cut0.p, S.cut_rec.p};
+    }
     const bool tracing = std::getenv("BPE355_TRACE") != nullptr;
     if (tracing) S.rstats.reserve(3);
     unsigned long long pend_entries = 0;   // blocks handed out x kPendBlock (the last attempt's)
@@ -1787,7 +1976,7 @@ size_t encode_device(bpe_tokenizer& T, const uint8_t* d_text, size_t n, OutT* d_
                    cap - 1, (unsigned long long)(cap / 2), fill.p, T.recs_cache.p, rec_cap, rec_region, rec_fill.p,
                    rec_base.p, rec_n.p, pend_blocks ? S.pend.p : nullptr, pend_blocks, S.pend_nblk.p,
                    S.block_used.p, status.p};
-        hipLaunchKernelGGL(kern, dim3(sgrid), dim3(256), kStage, s, A, D);
+        hipLaunchKernelGGL(kern, dim3(sgrid), dim3(256), kStage, s, A, D, SC);
         BPE_HIP(hipGetLastError());
         unsigned nblk = 0;
         to_host(&nblk, S.pend_nblk.p, 4, s);
@@ -1923,6 +2112,36 @@ size_t encode_device(bpe_tokenizer& T, const uint8_t* d_text, size_t n, OutT* d_
         hipLaunchKernelGGL(wk, dim3(wgrid), dim3(256), 0, s, EA, d_out);
         BPE_HIP(hipGetLastError());
     }
+    if (docs) {   // the documents' id offsets: the cuts' (from the kept attempt's scan), then one gather
+        if (want_cuts) {
+            int o_cu = 0;
+            BPE_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o_cu, k_enc_cut_offsets, 256, 0));
+            const unsigned ogrid = (unsigned)std::min<size_t>(n_parts, (size_t)std::max(1, o_cu) * std::max(1, n_cu) * 2);
+            hipLaunchKernelGGL(k_enc_cut_offsets, dim3(ogrid), dim3(256), 0, s, EA, S.chunk_cut0.p, S.cut_rec.p,
+                               S.cut_off.p);
+            BPE_HIP(hipGetLastError());
+        }
+        const size_t nd = docs->n_docs + 1;
+        // every start after the first a cut of its own (no empty document): document i is cut
+        // i - 1 and the gather needs no table; else each document's cut, from the host
+        const bool one_to_one = cuts.size() + 1 == docs->n_docs;
+        if (!one_to_one) {
+            std::vector<uint32_t> dc(nd);
+            size_t j = 0;
+            for (size_t i = 0; i < docs->n_docs; ++i) {
+                const unsigned long long st = docs->starts[i];
+                while (j < cuts.size() && cuts[j] < st) ++j;
+                dc[i] = st == 0 ? kDocAtZero : st >= n ? kDocAtEnd : (uint32_t)j;
+            }
+            dc[docs->n_docs] = kDocAtEnd;
+            S.doc_cut.reserve(nd);
+            to_device(S.doc_cut.p, dc.data(), nd * 4, s);
+        }
+        hipLaunchKernelGGL(k_enc_doc_offsets, dim3(grid_for(nd, 256)), dim3(256), 0, s,
+                           one_to_one ? nullptr : S.doc_cut.p, nd, S.cut_off.p,
+                           coff.p, ctot.p, n_parts, docs->d_out);
+        BPE_HIP(hipGetLastError());
+    }
     unsigned long long last[2] = {0, 0};
     unsigned st = 0;
     to_host(&last[0], coff.p + n_parts - 1, 8, s);
@@ -2023,6 +2242,18 @@ size_t encode_gpus(bpe_tokenizer& T, const uint8_t* utf8, size_t n, uint32_t* id
         m += ids[r].size();
     }
     return m;
+}
+
+// encode_batch's document starts, checked, as encode_device's cuts
+std::vector<unsigned long long> batch_cuts(const uint64_t* starts, size_t n_docs, size_t n) {
+    BPE_REQUIRE(n_docs == 0 || starts, BPE_E_ARG, "NULL doc_starts");
+    BPE_REQUIRE(n_docs > 0 || n == 0, BPE_E_ARG, "text without a document");
+    BPE_REQUIRE(n_docs < (1ull << 60), BPE_E_ARG, "too many documents");
+    BPE_REQUIRE(n_docs == 0 || starts[0] == 0, BPE_E_ARG, "doc_starts[0] must be 0");
+    for (size_t i = 1; i < n_docs; ++i)
+        BPE_REQUIRE(starts[i] >= starts[i - 1], BPE_E_ARG, "doc_starts must not decrease");
+    BPE_REQUIRE(n_docs == 0 || starts[n_docs - 1] <= n, BPE_E_ARG, "a document starts past the end of the text");
+    return std::vector<unsigned long long>(starts, starts + n_docs);
 }
 
 template <class F>
@@ -2416,6 +2647,77 @@ int bpe_tok_encode_chunks(bpe_tokenizer* tok, const uint8_t* utf8, size_t n, con
         if (m) BPE_HIP(hipMemcpyAsync(ids_out, d_out.p, m * 4, hipMemcpyDeviceToHost, tok->stream));
         BPE_HIP(hipStreamSynchronize(tok->stream));
         *n_out = m;
+    });
+}
+
+int bpe_tok_encode_batch_device(bpe_tokenizer* tok, const uint8_t* d_utf8, size_t n, const uint64_t* doc_starts,
+                                size_t n_docs, uint32_t* d_out, size_t* n_out, uint64_t* d_id_offsets, void* hip_stream) {
+    return bpe::guarded_enc([&] {
+        BPE_REQUIRE(tok && n_out && d_id_offsets && (n == 0 || (d_utf8 && d_out)), BPE_E_ARG, "NULL argument");
+        const std::vector<unsigned long long> cuts = bpe::batch_cuts(doc_starts, n_docs, n);
+        hipStream_t s = hip_stream ? (hipStream_t)hip_stream : tok->stream;
+        *n_out = 0;
+        if (n == 0) {   // empty documents only: every offset is 0
+            BPE_HIP(hipMemsetAsync(d_id_offsets, 0, (n_docs + 1) * sizeof(uint64_t), s));
+            BPE_HIP(hipStreamSynchronize(s));
+            return;
+        }
+        const bpe::DocStarts docs{doc_starts, n_docs, reinterpret_cast<unsigned long long*>(d_id_offsets)};
+        *n_out = bpe::encode_device(*tok, d_utf8, n, d_out, s, cuts, &docs);
+    });
+}
+
+int bpe_tok_encode_batch(bpe_tokenizer* tok, const uint8_t* utf8, size_t n, const uint64_t* doc_starts,
+                         size_t n_docs, uint32_t* ids_out, size_t cap, size_t* n_out, uint64_t* id_offsets_out) {
+    return bpe::guarded_enc([&] {
+        BPE_REQUIRE(tok && n_out && id_offsets_out && (n == 0 || (utf8 && ids_out)), BPE_E_ARG, "NULL argument");
+        BPE_REQUIRE(cap >= n, BPE_E_ARG, "ids_out capacity must be >= input bytes");
+        const std::vector<unsigned long long> cuts = bpe::batch_cuts(doc_starts, n_docs, n);
+        *n_out = 0;
+        if (n == 0) {
+            std::fill(id_offsets_out, id_offsets_out + n_docs + 1, (uint64_t)0);
+            return;
+        }
+        bpe::DevBuf<uint8_t> d_text(n);
+        bpe::DevBuf<uint32_t> d_out(n);
+        bpe::DevBuf<unsigned long long> d_off(n_docs + 1);
+        BPE_HIP(hipMemcpyAsync(d_text.p, utf8, n, hipMemcpyHostToDevice, tok->stream));
+        const bpe::DocStarts docs{doc_starts, n_docs, d_off.p};
+        const size_t m = bpe::encode_device(*tok, d_text.p, n, d_out.p, tok->stream, cuts, &docs);
+        if (m) BPE_HIP(hipMemcpyAsync(ids_out, d_out.p, m * 4, hipMemcpyDeviceToHost, tok->stream));
+        BPE_HIP(hipMemcpyAsync(id_offsets_out, d_off.p, (n_docs + 1) * 8, hipMemcpyDeviceToHost, tok->stream));
+        BPE_HIP(hipStreamSynchronize(tok->stream));
+        *n_out = m;
+    });
+}
+
+int bpe_ids_pack_rows_device(const uint32_t* d_ids, const uint64_t* d_offsets, size_t n_rows, size_t row_len,
+                             int64_t pad, int flags, int elem_bytes, void* d_out, int32_t* d_lengths,
+                             void* hip_stream) {
+    return bpe::guarded_enc([&] {
+        BPE_REQUIRE(elem_bytes == 4 || elem_bytes == 8, BPE_E_ARG, "elem_bytes must be 4 or 8");
+        BPE_REQUIRE((flags & ~(bpe::kPackKeepLast | bpe::kPackPadLeft)) == 0, BPE_E_ARG, "unknown flags");
+        BPE_REQUIRE(elem_bytes == 8 || (pad >= INT32_MIN && pad <= INT32_MAX), BPE_E_ARG, "pad does not fit int32");
+        BPE_REQUIRE(row_len <= (size_t)INT32_MAX, BPE_E_ARG, "row_len does not fit the int32 lengths");
+        if (n_rows == 0) return;
+        BPE_REQUIRE(d_offsets && d_lengths && (row_len == 0 || d_out), BPE_E_ARG, "NULL argument");
+        BPE_REQUIRE(row_len == 0 || n_rows <= SIZE_MAX / 8 / row_len, BPE_E_ARG, "n_rows x row_len overflows");
+        hipStream_t s = (hipStream_t)hip_stream;
+        const size_t per = 16 / (size_t)elem_bytes;
+        const bool vec = row_len % per == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0;
+        const unsigned grid = bpe::grid_for(std::max(n_rows, n_rows * row_len / (vec ? per : 1)), 256);
+        const unsigned long long* off = reinterpret_cast<const unsigned long long*>(d_offsets);
+        if (elem_bytes == 4) {
+            auto k = vec ? bpe::k_pack_rows<int32_t, true> : bpe::k_pack_rows<int32_t, false>;
+            hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, s, d_ids, off, n_rows, row_len, (int32_t)pad, flags,
+                               static_cast<int32_t*>(d_out), d_lengths);
+        } else {
+            auto k = vec ? bpe::k_pack_rows<int64_t, true> : bpe::k_pack_rows<int64_t, false>;
+            hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, s, d_ids, off, n_rows, row_len, pad, flags,
+                               static_cast<int64_t*>(d_out), d_lengths);
+        }
+        BPE_HIP(hipGetLastError());
+        BPE_HIP(hipStreamSynchronize(s));
     });
 }
 
