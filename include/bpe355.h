@@ -271,6 +271,40 @@ int bpe_dec_decode(bpe_decoder* dec, const uint32_t* ids, size_t n, uint8_t* out
 /* device ids -> device bytes */
 int bpe_dec_decode_device(bpe_decoder* dec, const uint32_t* d_ids, size_t n, uint8_t* d_out, size_t cap,
                           size_t* n_out, void* hip_stream);
+/* Batch decode: decode(ids[id_offsets[i] : id_offsets[i+1]]) for every row i, the rows' bytes
+ * concatenated, in one launch sequence without a size-query pass.
+ * id_offsets: n_rows + 1 entries, id_offsets[0] == 0, non-decreasing, last == n, else BPE_E_ARG
+ * (equal neighbours: an empty row).  *bytes_out: malloc'ed, release with bpe_blob_free (never NULL
+ * on success, also for 0 bytes).  byte_offsets_out: n_rows + 1 entries: row i's bytes are
+ * bytes[byte_offsets[i] : byte_offsets[i+1]).  token_offsets_out: NULL, or n + 1 entries: token
+ * j's bytes are bytes[token_offsets[j] : token_offsets[j+1]).  An id without a vocab entry:
+ * BPE_E_KEY, message = the id, the first such id in flat order.  n == 0 and n_rows == 0 are valid. */
+int bpe_dec_decode_batch(bpe_decoder* dec, const uint32_t* ids, size_t n, const uint64_t* id_offsets,
+                         size_t n_rows, uint8_t** bytes_out, size_t* n_bytes,
+                         uint64_t* byte_offsets_out, uint64_t* token_offsets_out);
+/* same, everything in device memory (d_id_offsets too: it is checked on the device); cap too small:
+ * BPE_E_ARG with *n_out = bytes needed, as bpe_dec_decode_device (d_byte_offsets and d_token_offsets
+ * are written then as well).  d_token_offsets may be NULL.  hip_stream NULL: the decoder's own
+ * stream, as in bpe_dec_decode_device.  Returns once d_out is written.  The decoder keeps the
+ * batch calls' device arrays between calls while they take at most 64 MiB; one call at a time
+ * uses them (the calls of several threads on one decoder take turns). */
+int bpe_dec_decode_batch_device(bpe_decoder* dec, const uint32_t* d_ids, size_t n,
+                                const uint64_t* d_id_offsets, size_t n_rows, uint8_t* d_out, size_t cap,
+                                size_t* n_out, uint64_t* d_byte_offsets, uint64_t* d_token_offsets,
+                                void* hip_stream);
+/* A dense [n_rows, row_len] matrix of ids in device memory (elem_bytes 4: int32, 8: int64), as
+ * bpe_ids_pack_rows_device writes it or a generation loop fills it, -> host bytes and row offsets
+ * as bpe_dec_decode_batch returns them; the ids never visit the host.  The kept span of row i:
+ * with d_lengths (int32, n_rows entries) its first d_lengths[i] entries (flags & 2: its last, a
+ * left-padded row), without (NULL) all row_len; with stop_id >= 0 the span ends before the first
+ * entry equal to stop_id (flags & 1: after it).  A length outside [0, row_len]: BPE_E_ARG.
+ * Entries outside the kept span are never inspected (any pad value is legal there); a kept entry
+ * outside [0, 2^32) or without a vocab entry: BPE_E_KEY, message = the entry in decimal, the first
+ * such entry in row-major order.  n_rows == 0 and row_len == 0 are valid. */
+int bpe_dec_decode_rows_device(bpe_decoder* dec, const void* d_rows, int elem_bytes, size_t n_rows,
+                               size_t row_len, const int32_t* d_lengths, int64_t stop_id, int flags,
+                               uint8_t** bytes_out, size_t* n_bytes, uint64_t* byte_offsets_out,
+                               void* hip_stream);
 void bpe_dec_free(bpe_decoder* dec);
 
 /* ---------------------------------------------------------------- bulk encode plumbing */

@@ -120,6 +120,10 @@ _SIGS = [
     ("bpe_dec_create", ctypes.c_int, [_U8P, _SZ, ctypes.POINTER(_P)]),
     ("bpe_dec_decode", ctypes.c_int, [_P, _P, _SZ, _P, _SZ, ctypes.POINTER(_SZ)]),
     ("bpe_dec_decode_device", ctypes.c_int, [_P, _P, _SZ, _P, _SZ, ctypes.POINTER(_SZ), _P]),
+    ("bpe_dec_decode_batch", ctypes.c_int, [_P, _P, _SZ, _P, _SZ, ctypes.POINTER(_P), ctypes.POINTER(_SZ), _P, _P]),
+    ("bpe_dec_decode_batch_device", ctypes.c_int, [_P, _P, _SZ, _P, _SZ, _P, _SZ, ctypes.POINTER(_SZ), _P, _P, _P]),
+    ("bpe_dec_decode_rows_device", ctypes.c_int, [_P, _P, ctypes.c_int, _SZ, _SZ, _P, ctypes.c_int64, ctypes.c_int,
+                                                  ctypes.POINTER(_P), ctypes.POINTER(_SZ), _P, _P]),
     ("bpe_dec_free", None, [_P]),
     ("bpe_read_file_device", ctypes.c_int, [ctypes.c_char_p, _P, _SZ, ctypes.POINTER(_SZ)]),
     ("bpe_copy_to_host", ctypes.c_int, [_P, _SZ, _P]),

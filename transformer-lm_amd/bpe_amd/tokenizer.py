@@ -8,6 +8,7 @@ from_files() are host-side byte/pickle plumbing, as in the reference.
 from __future__ import annotations
 
 import ctypes
+import itertools
 import os
 import pickle
 from typing import Iterable, Iterator, List, Tuple
@@ -271,6 +272,159 @@ class Tokenizer:
         _lib.check(L.bpe_dec_decode(self._decoder(), arr, len(ids), buf, n_out.value, ctypes.byref(n_out)),
                    "decode")
         return bytes(buf[:n_out.value]).decode("utf-8", errors="replace")
+
+    # ------------------------------------------------------------------ batch decode
+    # decode(r) for every row r in one launch sequence (bpe_dec_decode_batch: the lengths of all
+    # ids, one scan, one tiled gather, no size-query pass), the other half of the batch encode.
+    # The library returns the rows' bytes concatenated and where each row begins; the string forms
+    # slice that buffer and run CPython's decoder with errors="replace" on every slice, so the
+    # replacement rule applies per row exactly as in separate decode() calls.  On the current
+    # device, like the batch encode.
+    def _check_ids(self, ids) -> None:
+        """What decode() raises for an id the uint32 device table cannot hold."""
+        for i in ids:
+            if not isinstance(i, int) or i < 0 or i > 0xFFFFFFFF:
+                v = self.vocab[i]   # KeyError, as the reference's lookup raises
+                if not isinstance(v, (bytes, bytearray)):
+                    raise TypeError(f"sequence item: expected a bytes-like object, {type(v).__name__} found")
+                raise KeyError(i)
+
+    def _flatten(self, rows):
+        """rows of ids -> (ids np.uint32 [total], offsets np.uint64 [len(rows) + 1]); an id decode()
+        would refuse raises what decode() raises, for the first such row."""
+        import numpy as np
+        rows = [list(r) for r in rows]
+        offsets = np.zeros(len(rows) + 1, dtype=np.uint64)
+        if rows:
+            np.cumsum(np.fromiter(map(len, rows), dtype=np.uint64, count=len(rows)), out=offsets[1:])
+        flat = list(itertools.chain.from_iterable(rows))
+        ids = None
+        if set(map(type, flat)) <= {int}:   # the common case, checked without a Python-level loop
+            try:
+                a = np.array(flat, dtype=np.int64)
+            except OverflowError:
+                a = None
+            if a is not None and (a.size == 0 or (int(a.min()) >= 0 and int(a.max()) <= 0xFFFFFFFF)):
+                ids = a.astype(np.uint32)
+        if ids is None:
+            for r in rows:
+                self._check_ids(r)
+            ids = np.array([int(i) for i in flat], dtype=np.int64).astype(np.uint32)   # bool, int subclasses
+        return ids, offsets
+
+    @staticmethod
+    def _decode_status(rc: int, what: str) -> None:
+        if rc == _lib.BPE_E_KEY:   # vocab[i] of an id without an entry
+            raise KeyError(int((_lib.lib().bpe_last_error() or b"0").decode()))
+        _lib.check(rc, what)
+
+    def _decode_csr(self, ids, offsets, want_token_offsets: bool = False):
+        """ids np.uint32, offsets np.uint64 (both contiguous) -> (bytes of all rows, byte offsets
+        np.uint64 [rows + 1], token offsets np.uint64 [len(ids) + 1] or None)."""
+        import numpy as np
+        dec = self._decoder()
+        L = _lib.lib()
+        n, nr = int(ids.size), int(offsets.size) - 1
+        byte_off = np.zeros(nr + 1, dtype=np.uint64)
+        tok_off = np.zeros(n + 1, dtype=np.uint64) if want_token_offsets else None
+        p, nb = ctypes.c_void_p(), ctypes.c_size_t(0)
+        rc = L.bpe_dec_decode_batch(dec, ids.ctypes.data, n, offsets.ctypes.data, nr, ctypes.byref(p), ctypes.byref(nb),
+                                    byte_off.ctypes.data, tok_off.ctypes.data if want_token_offsets else None)
+        self._decode_status(rc, "decode_batch")
+        try:
+            data = ctypes.string_at(p, nb.value)
+        finally:
+            L.bpe_blob_free(p)
+        return data, byte_off, tok_off
+
+    def decode_batch_bytes(self, rows) -> List[bytes]:
+        """[b"".join(vocab[i] for i in r) for r in rows]: the rows' raw bytes before UTF-8 decoding,
+        one library call (see decode_batch)."""
+        self._decoder()
+        data, byte_off, _ = self._decode_csr(*self._flatten(rows))
+        off = byte_off.tolist()
+        return [data[a:b] for a, b in zip(off, off[1:])]
+
+    def decode_batch(self, rows) -> List[str]:
+        """[decode(r) for r in rows] in one library call, with decode()'s exceptions for the first
+        offending row (KeyError(id) for an id without a vocab entry)."""
+        return [b.decode("utf-8", errors="replace") for b in self.decode_batch_bytes(rows)]
+
+    def decode_tokens(self, ids) -> List[str]:
+        """[decode([i]) for i in ids] in one library call: one row per id."""
+        return self.decode_batch([(i,) for i in ids])
+
+    def decode_batch_np(self, ids, offsets, return_token_offsets: bool = False):
+        """CSR ids, as encode_batch_np returns them -> (bytes np.uint8 [total], byte_offsets np.int64
+        [rows + 1]): row i's bytes are bytes[byte_offsets[i]:byte_offsets[i + 1]].  With
+        return_token_offsets also token_offsets np.int64 [len(ids) + 1]: token j's bytes are
+        bytes[token_offsets[j]:token_offsets[j + 1]]."""
+        import numpy as np
+        self._decoder()
+        ids, offsets = np.asarray(ids), np.asarray(offsets)
+        if ids.ndim != 1 or offsets.ndim != 1 or ids.dtype.kind not in "iu" or offsets.dtype.kind not in "iu":
+            raise ValueError("ids and offsets are 1-D integer arrays")
+        if ids.dtype != np.uint32:
+            bad = np.flatnonzero((ids < 0) | (ids > 0xFFFFFFFF))
+            if bad.size:
+                raise KeyError(int(ids[bad[0]]))
+        if offsets.size == 0 or offsets[0] != 0 or offsets[-1] != ids.size or (np.diff(offsets.astype(np.int64)) < 0).any():
+            raise ValueError("offsets start at 0, do not decrease and end at len(ids)")
+        data, byte_off, tok_off = self._decode_csr(np.ascontiguousarray(ids, dtype=np.uint32),
+                                                   np.ascontiguousarray(offsets, dtype=np.uint64),
+                                                   return_token_offsets)
+        out = (np.frombuffer(data, dtype=np.uint8).copy(), byte_off.astype(np.int64))
+        return out + (tok_off.astype(np.int64),) if return_token_offsets else out
+
+    def decode_batch_padded(self, rows, lengths=None, *, stop_id: int | None = None, include_stop: bool = False,
+                            padding_side: str = "right") -> List[str]:
+        """A [B, T] torch.int32 / torch.int64 tensor of ids -> B strings; the ids never visit the
+        host (bpe_dec_decode_rows_device), only the bytes and the row offsets come back.  Row i is
+        decoded over its kept span: its first lengths[i] entries (padding_side="left": its last),
+        or all T when lengths is None; with stop_id, up to the first entry equal to it
+        (include_stop: that entry too).  What lies outside the span is never looked at, so any pad
+        value may stand there.  encode_batch_padded's (tensor, lengths) decode back with the same
+        padding_side.  A tensor on the current GPU is used in place (made contiguous if it is
+        not); anything else is moved there."""
+        import torch
+        if padding_side not in ("right", "left"):
+            raise ValueError("padding_side is 'right' or 'left'")
+        if not isinstance(rows, torch.Tensor):
+            rows = torch.as_tensor(rows)
+        if rows.dtype not in (torch.int32, torch.int64):
+            raise ValueError("rows is a torch.int32 or torch.int64 tensor")
+        if rows.dim() != 2:
+            raise ValueError("rows is a 2-D tensor [B, T]")
+        if stop_id is not None and not 0 <= int(stop_id) <= 0xFFFFFFFF:
+            raise ValueError("stop_id is an id in [0, 2^32) or None")
+        B, T = int(rows.shape[0]), int(rows.shape[1])
+        dec = self._decoder()
+        L = _lib.lib()
+        import numpy as np
+        dev = torch.device("cuda", torch.cuda.current_device())
+        rows = rows.to(dev).contiguous()
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).contiguous()
+            if lengths.dim() != 1 or lengths.shape[0] != B:
+                raise ValueError("lengths has one entry per row")
+        stream = torch.cuda.current_stream()
+        stream.synchronize()   # the rows are complete before the library's stream reads them
+        byte_off = np.zeros(B + 1, dtype=np.uint64)
+        p, nb = ctypes.c_void_p(), ctypes.c_size_t(0)
+        flags = (1 if include_stop else 0) | (2 if padding_side == "left" else 0)
+        rc = L.bpe_dec_decode_rows_device(dec, ctypes.c_void_p(rows.data_ptr()), rows.element_size(), B, T,
+                                          ctypes.c_void_p(lengths.data_ptr()) if lengths is not None else None,
+                                          -1 if stop_id is None else int(stop_id), flags, ctypes.byref(p),
+                                          ctypes.byref(nb), byte_off.ctypes.data, ctypes.c_void_p(stream.cuda_stream))
+        if rc == _lib.BPE_E_ARG:
+            raise ValueError((L.bpe_last_error() or b"").decode("utf-8", "replace"))
+        self._decode_status(rc, "decode_batch_padded")
+        try:
+            data = ctypes.string_at(p, nb.value)
+        finally:
+            L.bpe_blob_free(p)
+        off = byte_off.tolist()
+        return [data[a:b].decode("utf-8", errors="replace") for a, b in zip(off, off[1:])]
 
     def save(self, path: str, prefix: str = ""):
         os.makedirs(path, exist_ok=True)
