@@ -172,6 +172,68 @@ typedef struct {
 int bpe_result_stats(const bpe_result* r, bpe_train_stats* out);
 void bpe_result_free(bpe_result* r);
 
+/* ---------------------------------------------------------------- word counter */
+/* A device-resident {pre-token -> count} table that accumulates over many inputs and can be
+ * trained on: many files, a file larger than HBM (counted window by window), pre-counted words,
+ * several vocab sizes or special-token lists from one count.  The reference's trainer sees its
+ * corpus only through that multiset (train.py:16-49), so the result is bit-identical to training
+ * on the inputs as the reference would see them.
+ *  - Each bpe_counter_add_* call is one document: its pre-tokens end at its ends, exactly as a
+ *    separate extract_subword_frequencies (train.py:16-28) on that input would have them.
+ *  - The counter is independent of special tokens: it keeps every multi-byte pre-token, and
+ *    bpe_counter_words / bpe_counter_train leave out the words equal to a special (train.py:25).
+ *  - Training reads the counter and leaves it as it was: add more and train again.
+ *  - One device: the one current at bpe_counter_create.  The ranks of a larger job can each
+ *    count their shards, export them with bpe_counter_words and bpe_counter_add_words them into
+ *    one counter.  Calls of several threads on one counter take turns; different counters run
+ *    side by side.
+ *  - Limits (BPE_E_LIMIT, nothing wraps): a pre-token of 8 MiB or more; 2^40 bytes of distinct
+ *    words; 2^31 distinct words; the sum over all words of count x length at 2^62 or more (the
+ *    merge loop counts pairs in signed 64-bit integers), checked by bpe_counter_add_words,
+ *    bpe_counter_absorb and bpe_counter_train. */
+typedef struct bpe_counter bpe_counter;
+typedef struct {
+    uint64_t n_words;           /* distinct multi-byte pre-tokens held */
+    uint64_t n_pretokens;       /* their summed counts */
+    uint64_t n_bytes;           /* text bytes counted (after newline translation; none for add_words) */
+    uint64_t n_inputs;          /* bpe_counter_add_* calls that succeeded */
+    uint64_t n_windows;         /* windows those inputs were counted in */
+    uint64_t max_window_bytes;  /* the longest of them */
+    uint64_t table_slots;       /* slots of the word table (load <= 1/2) */
+    uint64_t pool_bytes;        /* capacity of the byte pool that holds the words */
+    uint64_t pool_live_bytes;   /* bytes of it that words occupy (a word's bytes are stored once) */
+    uint64_t n_grows;           /* table rehashes and pool reallocations so far */
+    double t_fold_ms;           /* host time spent merging counted tables into the counter */
+} bpe_counter_info_t;
+int bpe_counter_create(bpe_counter** out);
+/* The file at path as bpe_train_file reads it (strict UTF-8, universal newlines; BPE_E_IO,
+ * BPE_E_UTF8 with the byte's position in the file), counted in windows of about window_bytes
+ * (0: the default, 8 GiB -- a choice, not a measured optimum; at least 64 KiB) cut at safe split
+ * points, so that HBM holds one window (plus about 4 bytes of scratch per byte) at a time.  All or
+ * nothing: after an error the counter holds what it held before. */
+int bpe_counter_add_file(bpe_counter* c, const char* path, size_t window_bytes);
+/* raw file bytes in host memory: one document */
+int bpe_counter_add_buffer(bpe_counter* c, const uint8_t* data, size_t n);
+/* the same, bytes in device memory on the counter's device (not modified); stream may be NULL */
+int bpe_counter_add_device(bpe_counter* c, const uint8_t* d_data, size_t n, void* hip_stream);
+/* (u32 len, bytes, u64 count) records as bpe_word_counts and bpe_counter_words return them; words
+ * under 2 bytes are dropped, equal words summed.  A truncated blob: BPE_E_ARG, counter unchanged. */
+int bpe_counter_add_words(bpe_counter* c, const uint8_t* blob, size_t blob_n);
+/* dst += src; src is unchanged; both on one device */
+int bpe_counter_absorb(bpe_counter* dst, const bpe_counter* src);
+/* The words not equal to a special and their counts, packed on the device and copied out once:
+ * (u32 len, bytes, u64 count) records in no particular order; release with bpe_blob_free. */
+int bpe_counter_words(const bpe_counter* c, const char* const* specials, int n_specials, uint8_t** blob,
+                      size_t* blob_n);
+/* train_bpe on the counted words.  The stats carry the accumulated n_bytes and n_pretokens,
+ * t_load_ms and t_count_ms summed over the add calls, and the training's own fields as usual. */
+int bpe_counter_train(const bpe_counter* c, int vocab_size, const char* const* specials, int n_specials,
+                      bpe_result** out);
+int bpe_counter_info(const bpe_counter* c, bpe_counter_info_t* out);
+/* forget every word; the device memory is kept for the next inputs */
+void bpe_counter_clear(bpe_counter* c);
+void bpe_counter_free(bpe_counter* c);
+
 /* Hands back the device memory the trainer keeps between calls so that a repeated train_bpe
  * does not pay for fresh allocations: the corpus buffer (drive.hip), the counter's record pool
  * and aggregation bins (count.hip; about 2 x 2 bytes per corpus byte), for `device` (< 0: every

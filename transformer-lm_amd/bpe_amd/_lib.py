@@ -53,6 +53,15 @@ class TrainStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class CounterInfo(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in (
+        "n_words", "n_pretokens", "n_bytes", "n_inputs", "n_windows", "max_window_bytes",
+        "table_slots", "pool_bytes", "pool_live_bytes", "n_grows")] + [("t_fold_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 HOST_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p,
                                      ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t)
 
@@ -90,6 +99,19 @@ _SIGS = [
     ("bpe_word_counts", ctypes.c_int, [_U8P, _SZ, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int,
                                        ctypes.POINTER(_P), ctypes.POINTER(_SZ)]),
     ("bpe_blob_free", None, [_P]),
+    ("bpe_counter_create", ctypes.c_int, [ctypes.POINTER(_P)]),
+    ("bpe_counter_add_file", ctypes.c_int, [_P, ctypes.c_char_p, _SZ]),
+    ("bpe_counter_add_buffer", ctypes.c_int, [_P, _U8P, _SZ]),
+    ("bpe_counter_add_device", ctypes.c_int, [_P, _P, _SZ, _P]),
+    ("bpe_counter_add_words", ctypes.c_int, [_P, _U8P, _SZ]),
+    ("bpe_counter_absorb", ctypes.c_int, [_P, _P]),
+    ("bpe_counter_words", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int,
+                                         ctypes.POINTER(_P), ctypes.POINTER(_SZ)]),
+    ("bpe_counter_train", ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int,
+                                         ctypes.POINTER(_P)]),
+    ("bpe_counter_info", ctypes.c_int, [_P, _P]),
+    ("bpe_counter_clear", None, [_P]),
+    ("bpe_counter_free", None, [_P]),
     ("bpe_result_n_merges", ctypes.c_int64, [_P]),
     ("bpe_result_n_vocab", ctypes.c_int64, [_P]),
     ("bpe_result_merges_blob", _SZ, [_P, ctypes.POINTER(_P)]),

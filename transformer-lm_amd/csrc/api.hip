@@ -110,6 +110,11 @@ struct bpe_comm {
     std::unique_ptr<bpe::Comm> impl;
 };
 
+struct bpe_counter {
+    mutable std::mutex m;   // one call at a time per counter
+    bpe::WordAccumulator acc;
+};
+
 namespace bpe {
 std::unique_ptr<Comm> make_rccl_comm(const uint8_t id[128], int nranks, int rank, int device);
 std::unique_ptr<Comm> make_host_comm(bpe_host_allreduce_fn fn, void* ctx, int nranks, int rank,
@@ -337,6 +342,113 @@ int bpe_word_counts(const uint8_t* data, size_t n, const char* const* specials, 
 }
 
 void bpe_blob_free(uint8_t* blob) { std::free(blob); }
+
+int bpe_counter_create(bpe_counter** out) {
+    return bpe::guarded([&] {
+        BPE_REQUIRE(out, BPE_E_ARG, "out is NULL");
+        *out = nullptr;
+        bpe::DeviceGuard::require();
+        *out = new bpe_counter;
+    });
+}
+
+int bpe_counter_add_file(bpe_counter* c, const char* path, size_t window_bytes) {
+    return bpe::guarded([&] {
+        BPE_REQUIRE(c, BPE_E_ARG, "counter is NULL");
+        BPE_REQUIRE(path, BPE_E_ARG, "path is NULL");
+        const bpe::Source src = bpe::Source::open_path(path);
+        std::lock_guard<std::mutex> g(c->m);
+        bpe::counter_add_source(c->acc, src, window_bytes);
+    });
+}
+
+int bpe_counter_add_buffer(bpe_counter* c, const uint8_t* data, size_t n) {
+    return bpe::guarded([&] {
+        BPE_REQUIRE(c, BPE_E_ARG, "counter is NULL");
+        BPE_REQUIRE(!n || data, BPE_E_ARG, "data is NULL");
+        const bpe::Source src = bpe::Source::memory(data, n);
+        std::lock_guard<std::mutex> g(c->m);
+        bpe::counter_add_source(c->acc, src, 0);
+    });
+}
+
+int bpe_counter_add_device(bpe_counter* c, const uint8_t* d_data, size_t n, void* hip_stream) {
+    return bpe::guarded([&] {
+        BPE_REQUIRE(c, BPE_E_ARG, "counter is NULL");
+        BPE_REQUIRE(!n || d_data, BPE_E_ARG, "data is NULL");
+        std::lock_guard<std::mutex> g(c->m);
+        bpe::counter_add_device(c->acc, d_data, n, (hipStream_t)hip_stream);
+    });
+}
+
+int bpe_counter_add_words(bpe_counter* c, const uint8_t* blob, size_t blob_n) {
+    return bpe::guarded([&] {
+        BPE_REQUIRE(c, BPE_E_ARG, "counter is NULL");
+        BPE_REQUIRE(!blob_n || blob, BPE_E_ARG, "blob is NULL");
+        std::lock_guard<std::mutex> g(c->m);
+        c->acc.add_records(blob, blob_n);
+    });
+}
+
+int bpe_counter_absorb(bpe_counter* dst, const bpe_counter* src) {
+    return bpe::guarded([&] {
+        BPE_REQUIRE(dst && src, BPE_E_ARG, "counter is NULL");
+        BPE_REQUIRE(dst != src, BPE_E_ARG, "a counter cannot absorb itself");
+        std::scoped_lock g(dst->m, src->m);
+        dst->acc.absorb(src->acc);
+    });
+}
+
+int bpe_counter_words(const bpe_counter* c, const char* const* specials, int n_specials, uint8_t** blob,
+                      size_t* blob_n) {
+    return bpe::guarded([&] {
+        BPE_REQUIRE(blob && blob_n, BPE_E_ARG, "blob is NULL");
+        *blob = nullptr;
+        *blob_n = 0;
+        BPE_REQUIRE(c, BPE_E_ARG, "counter is NULL");
+        auto sp = bpe::to_specials(specials, n_specials);
+        std::lock_guard<std::mutex> g(c->m);
+        c->acc.export_words(sp, blob, blob_n);
+    });
+}
+
+int bpe_counter_train(const bpe_counter* c, int vocab_size, const char* const* specials, int n_specials,
+                      bpe_result** out) {
+    return bpe::guarded([&] {
+        BPE_REQUIRE(out, BPE_E_ARG, "out is NULL");
+        *out = nullptr;
+        BPE_REQUIRE(c, BPE_E_ARG, "counter is NULL");
+        auto sp = bpe::to_specials(specials, n_specials);
+        bpe::TrainOutput to;
+        {
+            std::lock_guard<std::mutex> g(c->m);
+            c->acc.train(vocab_size, sp, to);
+        }
+        auto r = std::make_unique<bpe_result>();
+        finish_result(to, sp, r.get());
+        *out = r.release();
+    });
+}
+
+int bpe_counter_info(const bpe_counter* c, bpe_counter_info_t* out) {
+    return bpe::guarded([&] {
+        BPE_REQUIRE(c && out, BPE_E_ARG, "counter or out is NULL");
+        std::lock_guard<std::mutex> g(c->m);
+        const bpe::AccumInfo i = c->acc.info();
+        *out = bpe_counter_info_t{i.n_words, i.n_pretokens, i.n_bytes, i.n_inputs, i.n_windows, i.max_window_bytes,
+                                  i.table_slots, i.pool_bytes, i.pool_live_bytes, i.n_grows, i.t_fold_ms};
+    });
+}
+
+void bpe_counter_clear(bpe_counter* c) {
+    if (!c) return;
+    (void)bpe::guarded([&] {
+        std::lock_guard<std::mutex> g(c->m);
+        c->acc.clear();
+    });
+}
+
+void bpe_counter_free(bpe_counter* c) { delete c; }
 
 size_t bpe_result_flat(const bpe_result* r, int which, const uint32_t** lens, const uint8_t** bytes,
                        size_t* n_bytes) {

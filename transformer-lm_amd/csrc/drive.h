@@ -38,9 +38,11 @@ void stage_to_device(const Source& src, size_t off, size_t len, uint8_t* d_dst, 
 // d_src[0, len) on `device` -> host memory h_dst (pageable), through pinned staging, `threads` copiers
 void device_to_host(const uint8_t* d_src, size_t len, uint8_t* h_dst, int device, int threads);
 // src[off, off + len) -> d_dst, validated and counted segment by segment as it arrives
-// (false: the text holds a \r, so the caller must apply universal newlines and count it whole)
+// (false: the text holds a \r, so the caller must apply universal newlines and count it whole).
+// min_cap: a lower bound (a power of two) for the word table's slots, when the caller knows
+// better than the size rule of the whole-corpus count (windows: counter_add_source)
 bool load_and_count(const Source& src, size_t off, size_t len, uint8_t* d_dst, int device, int threads,
-                    hipStream_t stream, Prepared& pre);
+                    hipStream_t stream, Prepared& pre, size_t min_cap = 0);
 std::vector<int> pick_devices(int n_gpus);
 // train_bpe over the whole source on n_gpus devices of this process (<= 0: all visible)
 void train_source(const Source& src, int vocab_size, const std::vector<std::string>& specials, int n_gpus,
@@ -49,6 +51,17 @@ void train_source(const Source& src, int vocab_size, const std::vector<std::stri
 // of which this rank reads its share
 void train_source_comm(const Source& src, bool split, int vocab_size, const std::vector<std::string>& specials,
                        Comm* comm, TrainOutput& out);
+// One document into a word accumulator without holding more than one window of it in HBM: the
+// source is cut into windows of about window_bytes (0: kDefaultWindow; at least 64 KiB) at safe
+// split points, each window is loaded, validated and counted into one reused corpus buffer and
+// folded.  All or nothing: after an error `acc` holds what it held before.  A UTF-8 error names
+// the byte's position in the source.
+// The default is a choice, not a measured optimum: 8 GiB of text plus the counter's scratch
+// (about 4 bytes per byte) is about 40 GB of HBM.
+constexpr size_t kDefaultWindow = (size_t)8 << 30;
+void counter_add_source(WordAccumulator& acc, const Source& src, size_t window_bytes);
+// the same for raw bytes already in device memory (one window; d_data is not modified)
+void counter_add_device(WordAccumulator& acc, const uint8_t* d_data, size_t n, hipStream_t stream);
 // bpe_release_device_memory: the corpus buffers kept for `dev` (< 0: every device) go back to the
 // device allocator; returns the bytes freed.  Buffers a running call holds are not touched, and the
 // cached copy streams are kept for the process (a concurrent transfer may be using them)

@@ -564,7 +564,7 @@ std::vector<size_t> segment_cuts(const Source& src, size_t off, size_t len, size
 }  // namespace
 
 bool load_and_count(const Source& src, size_t off, size_t len, uint8_t* d_dst, int device, int threads,
-                    hipStream_t stream, Prepared& pre) {
+                    hipStream_t stream, Prepared& pre, size_t min_cap) {
     const auto t0 = std::chrono::steady_clock::now();
     const std::vector<size_t> cut = segment_cuts(src, off, len, segment_bytes());
     const size_t chunks = (len + kStageChunk - 1) / kStageChunk;
@@ -612,7 +612,7 @@ bool load_and_count(const Source& src, size_t off, size_t len, uint8_t* d_dst, i
     const size_t agg_every = ae ? (size_t)std::max(0, std::atoi(ae)) : 4;
     try {
         vp.begin(d_dst, len, stream);
-        cp.begin(d_dst, len, CountPass::initial_cap(len), stream, timing_enabled());
+        cp.begin(d_dst, len, std::max(CountPass::initial_cap(len), min_cap), stream, timing_enabled());
         cp.gate = vp.flags.p;   // counts only text whose validation (earlier on the stream) passed
         size_t waited = 0;
         for (size_t k = 0; k + 1 < cut.size(); ++k) {
@@ -654,6 +654,136 @@ bool load_and_count(const Source& src, size_t off, size_t len, uint8_t* d_dst, i
     pre.t_count_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - load_ms;
     pre.load_ms = load_ms;
     return true;
+}
+
+// ------------------------------------------------------------------ windows into an accumulator
+namespace {
+
+// the first safe split point at or after `from` (a U+0020 between two ASCII non-space bytes, as
+// bpe_safe_split finds them looking back), or src.size
+size_t next_safe_split(const Source& src, size_t from) {
+    auto ascii_nonspace = [](uint8_t b) { return b < 0x80 && b != 0x20 && (b < 0x09 || b > 0x0D); };
+    std::vector<uint8_t> win((1u << 16) + 2);
+    for (size_t p = std::max<size_t>(from, 1); p + 1 < src.size;) {
+        const size_t lo = p - 1, hi = std::min(src.size, lo + win.size());
+        src.read(lo, hi - lo, win.data());
+        for (size_t i = 1; i + 1 < hi - lo; ++i)
+            if (win[i] == 0x20 && ascii_nonspace(win[i - 1]) && ascii_nonspace(win[i + 1])) return lo + i;
+        p = hi - 1;   // (the last byte read was only looked at as a right neighbour)
+    }
+    return src.size;
+}
+
+// [0, size) in windows of about `window` bytes: each ends at the last safe split point of its
+// final 64 KiB, or, when there is none, at the next one after it (in the worst case the source
+// is one window)
+std::vector<size_t> window_cuts(const Source& src, size_t window) {
+    std::vector<size_t> cut{0};
+    std::vector<uint8_t> win((1u << 16) + 2);
+    while (src.size - cut.back() > window) {
+        const size_t start = cut.back(), want = start + window;
+        const size_t lo = std::max(start, want - (win.size() - 2)), hi = std::min(src.size, want + 2);
+        src.read(lo, hi - lo, win.data());
+        const size_t p = bpe_safe_split(win.data(), hi - lo, want - lo);
+        size_t end = p > 0 && lo + p > start ? lo + p : next_safe_split(src, want);
+        if (end >= src.size) break;
+        cut.push_back(end);
+    }
+    cut.push_back(src.size);
+    return cut;
+}
+
+// Slots for a window's count table.  The whole-corpus rule (text.hip: n / 1024 past 64 MB) fits
+// a corpus of many GB, whose vocabulary has stopped growing; a window of a few GB holds more
+// distinct words per byte, overflows a table of that size and is then counted again, whole and
+// behind its load (measured: ~480 ms per 2 GiB window, profiles/r07).  So a window takes n / 128
+// slots, or four times the distinct words of the largest window counted so far if that is more.
+size_t window_table_slots(const WordAccumulator& a, const WordAccumulator& b, size_t len) {
+    const size_t seen = std::max(a.shard_words_hint(), b.shard_words_hint());
+    return next_pow2(std::max<size_t>(len / 128, 4 * seen));
+}
+
+// a window's UTF-8 error at its position in the source
+[[noreturn]] void rethrow_at(const Error& e, size_t offset) {
+    Error err = e;
+    const size_t p = err.msg.find("position ");
+    if (err.code == BPE_E_UTF8 && offset && p != std::string::npos)
+        err.msg = "'utf-8' codec can't decode byte at position " +
+                  std::to_string(std::stoull(err.msg.substr(p + 9)) + offset);
+    throw err;
+}
+
+}  // namespace
+
+void counter_add_source(WordAccumulator& acc, const Source& src, size_t window_bytes) {
+    const size_t window = std::max<size_t>(window_bytes ? window_bytes : kDefaultWindow, (size_t)64 << 10);
+    int cur = 0;
+    BPE_HIP(hipGetDevice(&cur));
+    const int dev = acc.device();
+    struct DevGuard { int prev; ~DevGuard() { (void)hipSetDevice(prev); } } dg{cur};
+    BPE_HIP(hipSetDevice(dev));
+    const std::vector<size_t> cut = window_cuts(src, window);
+    const size_t n_win = cut.size() - 1;
+    size_t max_win = 0;
+    for (size_t k = 0; k < n_win; ++k) max_win = std::max(max_win, cut[k + 1] - cut[k]);
+    // several windows go into an accumulator of their own, absorbed when the last one is in, so
+    // that an error in a later window leaves `acc` as it was
+    std::unique_ptr<WordAccumulator> tmp;
+    if (n_win > 1) tmp = std::make_unique<WordAccumulator>();
+    WordAccumulator& into = tmp ? *tmp : acc;
+    const hipStream_t s = into.stream();
+    std::unique_ptr<CorpusBuf> d = corpus_take(std::max<size_t>(max_win, 1));
+    struct Give { std::unique_ptr<CorpusBuf>& d; ~Give() { if (d) corpus_give(std::move(d)); } } give{d};
+    double load_ms = 0, count_ms = 0;
+    uint64_t n_bytes = 0;
+    for (size_t k = 0; k < n_win; ++k) {
+        const size_t off = cut[k], len = cut[k + 1] - off;
+        Prepared pre;
+        DevBuf<uint8_t> scratch;
+        const uint8_t* text = d->b.p;
+        size_t tn = len;
+        WordCounts wc;
+        try {
+            const auto t0 = std::chrono::steady_clock::now();
+            if (load_and_count(src, off, len, d->b.p, dev, io_threads(), s, pre, window_table_slots(into, acc, len))) {
+                wc = std::move(pre.wc);
+                load_ms += pre.load_ms;
+                count_ms += pre.t_count_ms;
+            } else {   // a \r in this window: universal newlines over the whole window, then the count
+                const double loaded = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+                text = prepare_text(d->b.p, len, scratch, &tn, s);
+                count_words(text, tn, wc, s, nullptr);
+                load_ms += loaded;
+                count_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - loaded;
+            }
+        } catch (const Error& e) {
+            (void)hipStreamSynchronize(s);
+            rethrow_at(e, off);
+        }
+        BPE_HIP(hipStreamSynchronize(s));
+        into.fold(text, wc, tn);   // returns once the buffer may take the next window
+        n_bytes += tn;
+    }
+    into.note_input(n_bytes, n_win, max_win, load_ms, count_ms);
+    if (tmp) acc.absorb(*tmp);
+}
+
+void counter_add_device(WordAccumulator& acc, const uint8_t* d_data, size_t n, hipStream_t stream) {
+    int cur = 0;
+    BPE_HIP(hipGetDevice(&cur));
+    struct DevGuard { int prev; ~DevGuard() { (void)hipSetDevice(prev); } } dg{cur};
+    BPE_HIP(hipSetDevice(acc.device()));
+    const hipStream_t s = stream ? stream : acc.stream();
+    const auto t0 = std::chrono::steady_clock::now();
+    DevBuf<uint8_t> scratch;
+    size_t tn = 0;
+    const uint8_t* text = prepare_text(d_data, n, scratch, &tn, s);
+    WordCounts wc;
+    count_words(text, tn, wc, s, nullptr);
+    BPE_HIP(hipStreamSynchronize(s));
+    const double count_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    acc.fold(text, wc, tn);
+    acc.note_input(tn, 1, n, 0, count_ms);
 }
 
 // ------------------------------------------------------------------ trainers

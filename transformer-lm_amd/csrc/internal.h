@@ -158,6 +158,75 @@ void train_on_device(const uint8_t* d_raw, size_t n, int vocab_size,
                      const std::vector<std::string>& specials, Comm* comm, hipStream_t stream,
                      TrainOutput& out, const TrainOpts& opt = TrainOpts{}, Prepared* pre = nullptr);
 
+// The merge loop on a word table whose words' bytes live in `text` (the corpus, a gathered buffer,
+// an accumulator's pool): base vocab, rounds, word build, merges into `out`; nothing when
+// vocab_size is not above the base vocab (merge_rounds <= 0).  The table is read, never changed;
+// drop_after_build (may be null) is released once the loop holds its own copy of the words.
+long long merge_rounds(int vocab_size, const std::vector<std::string>& specials);
+void train_words(const uint8_t* text, const WordCounts& wc, int vocab_size, const std::vector<std::string>& specials,
+                 hipStream_t stream, TrainOutput& out, Comm* loop_comm = nullptr,
+                 WordCounts* drop_after_build = nullptr);
+
+// ---------------------------------------------------------------- word accumulator (accum.hip)
+// A word table that owns its bytes and sums counts over many inputs: the {key, count} + pos
+// table of WordCounts over an append-only byte pool, which is the table's "text" (keys of words
+// longer than 7 bytes are len << 40 | pool offset + 1, pos[] of an inline word is its pool
+// offset).  One device (the one current at creation), one caller at a time.  Ranks of a larger
+// job can each count their shards and absorb one another's exported words (export_words ->
+// add_records).
+// Limits (BPE_E_LIMIT, never wrapped): a word of kMaxPretok bytes or more; pool offsets past
+// 2^40 - 2; 2^31 distinct words; and the sum over all words of count x length at 2^62 or more
+// -- the merge loop's pair counters are signed 64-bit (train.hip, PairsDev::cnt), and no pair
+// can occur more often than that sum.  The last is checked when words are added from records
+// and again at train().
+struct AccumInfo {
+    uint64_t n_words = 0, n_pretokens = 0, n_bytes = 0, n_inputs = 0, n_windows = 0, max_window_bytes = 0;
+    uint64_t table_slots = 0, pool_bytes = 0, pool_live_bytes = 0, n_grows = 0;
+    double t_load_ms = 0, t_count_ms = 0, t_fold_ms = 0;
+};
+class WordAccumulator {
+   public:
+    WordAccumulator();    // on the current device; BPE355_ACC_SLOTS / BPE355_ACC_POOL: initial sizes (tests)
+    ~WordAccumulator();
+    WordAccumulator(const WordAccumulator&) = delete;
+    WordAccumulator& operator=(const WordAccumulator&) = delete;
+    int device() const { return dev_; }
+    hipStream_t stream() const { return s_; }
+    // every word of a shard's table (bytes in `text`), counts summed; returns once `text` and
+    // `wc` are no longer needed.  weight: an upper bound of the shard's sum of count x length
+    // (its byte count).  Returns the shard's distinct words.
+    size_t fold(const uint8_t* text, const WordCounts& wc, uint64_t weight);
+    // the most distinct words any folded shard held: sizes the next window's count table
+    size_t shard_words_hint() const { return shard_words_; }
+    // (u32 len, bytes, u64 count) records in host memory; words under 2 bytes and zero counts are
+    // dropped.  A truncated blob: BPE_E_ARG, nothing added
+    void add_records(const uint8_t* blob, size_t n);
+    void absorb(const WordAccumulator& o);   // o unchanged; same device
+    // the words not equal to a special as (u32 len, bytes, u64 count) records, malloc'ed
+    void export_words(const std::vector<std::string>& specials, uint8_t** blob, size_t* blob_n) const;
+    void train(int vocab_size, const std::vector<std::string>& specials, TrainOutput& out) const;
+    void clear();
+    AccumInfo info() const;
+    // bookkeeping of the inputs (drive.hip): one add_* call, its windows, its timings
+    void note_input(uint64_t n_bytes, uint64_t n_windows, uint64_t max_window, double load_ms, double count_ms);
+
+   private:
+    struct Scratch;
+    void fold_list(const uint8_t* text, const unsigned long long* w_off, const uint32_t* w_len,
+                   const unsigned long long* w_cnt, size_t n);
+    size_t list_table(const unsigned long long* kv, const unsigned long long* pos, size_t cap, const uint8_t* text,
+                      const std::vector<std::string>& specials) const;
+    void ensure(size_t n_new, size_t new_bytes);
+    int dev_ = 0;
+    hipStream_t s_ = nullptr;
+    WordCounts wc_;              // kv, pos, cap (n_pretokens: the accumulated count)
+    DevBuf<uint8_t> pool_;       // (+ 16 bytes of padding past pool_cap_)
+    size_t pool_cap_ = 0, pool_used_ = 0, n_words_ = 0, shard_words_ = 0;
+    uint64_t weight_ = 0;        // upper bound of sum(count x length), saturating
+    AccumInfo st_;
+    std::unique_ptr<Scratch> sc_;   // grow-only device arrays of the folds and exports
+};
+
 bool timing_enabled();
 
 }  // namespace bpe

@@ -4363,11 +4363,7 @@ void train_on_device(const uint8_t* d_raw, size_t n, int vocab_size,
         else if (failed) throw err;
     }
 
-    // len(vocab) at loop start: Vocab(special_tokens) = specials then the 256 bytes, deduped
-    std::set<std::string> base;
-    for (const auto& s : specials) base.insert(s);
-    for (int b = 0; b < 256; ++b) base.insert(std::string(1, (char)b));
-    const long long rounds = (long long)vocab_size - (long long)base.size();
+    const long long rounds = merge_rounds(vocab_size, specials);
 
     out.stats.t_count_ms = ms_since(t1);
     out.stats.count_kernel_ms = count_ms;
@@ -4402,12 +4398,29 @@ void train_on_device(const uint8_t* d_raw, size_t n, int vocab_size,
         out.stats.t_total_ms = ms_since(t0);
         return;
     }
+    train_words(text, wc, vocab_size, specials, stream, out, loop_comm, &wc);
+    out.stats.t_total_ms = ms_since(t0);
+}
+
+long long merge_rounds(int vocab_size, const std::vector<std::string>& specials) {
+    // len(vocab) at loop start: Vocab(special_tokens) = specials then the 256 bytes, deduped
+    std::set<std::string> base;
+    for (const auto& s : specials) base.insert(s);
+    for (int b = 0; b < 256; ++b) base.insert(std::string(1, (char)b));
+    return (long long)vocab_size - (long long)base.size();
+}
+
+void train_words(const uint8_t* text, const WordCounts& wc, int vocab_size, const std::vector<std::string>& specials,
+                 hipStream_t stream, TrainOutput& out, Comm* loop_comm, WordCounts* drop_after_build) {
+    const long long rounds = merge_rounds(vocab_size, specials);
+    if (rounds <= 0) return;
+    BPE_REQUIRE(rounds < (1LL << 31) - 512, BPE_E_LIMIT, "vocab_size too large");
     auto go = [&](auto tag) {
         using TokT = decltype(tag);
         auto t2 = std::chrono::steady_clock::now();
         MergeLoop<TokT> loop(stream, loop_comm, text, (int)rounds, out);
         loop.build_words(wc, specials);
-        { WordCounts drop = std::move(wc); }
+        if (drop_after_build) { WordCounts drop = std::move(*drop_after_build); }
         out.stats.t_words_ms = ms_since(t2);
         auto t3 = std::chrono::steady_clock::now();
         loop.run();
@@ -4415,7 +4428,6 @@ void train_on_device(const uint8_t* d_raw, size_t n, int vocab_size,
     };
     if (256 + rounds + 1 < 65535) go(uint16_t{});
     else go(uint32_t{});
-    out.stats.t_total_ms = ms_since(t0);
 }
 
 }  // namespace bpe
