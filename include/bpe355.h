@@ -253,7 +253,8 @@ void bpe_set_timing(int enable);
  * (i64 id, u32 len, bytes) in the caller's dict order (the reverse map keeps the LAST id of a
  * duplicated byte string, tokenizer.py:19).  merges blob: u32 count + merge records.
  * specials: NULL/0 for none.  Missing specials are appended with ids len(vocab), ...
- * (tokenizer.py:35-38); their ids are reported by bpe_tok_special_id. */
+ * (tokenizer.py:35-38); their ids are reported by bpe_tok_special_id.  Vocab ids must lie in
+ * [0, 2^32), sparse or dense: the ids come out as uint32.  One outside: BPE_E_ARG. */
 int bpe_tok_create(const uint8_t* vocab_blob, size_t vocab_n, const uint8_t* merges_blob,
                    size_t merges_n, const char* const* specials, int n_specials,
                    bpe_tokenizer** out);
@@ -292,7 +293,10 @@ int bpe_tok_encode_batch_device(bpe_tokenizer* tok, const uint8_t* d_utf8, size_
 /* CSR ids (as the batch encode returns them) -> a dense [n_rows, row_len] matrix of int32
  * (elem_bytes 4) or int64 (8) in d_out, and d_lengths[i] = min(L_i, row_len).  A row longer than
  * row_len keeps its first ids (flags & 1: its last); a shorter one is filled with pad on the
- * right (flags & 2: on the left).  All pointers device memory; returns once the matrix is written. */
+ * right (flags & 2: on the left).  All pointers device memory; returns once the matrix is written.
+ * With elem_bytes 4 a kept id that does not fit int32 (2^31 or more) is an error, BPE_E_LIMIT with
+ * the smallest such id in the message, instead of a negative entry (the matrix is then not to be
+ * used); an id that the truncation drops is not looked at.  elem_bytes 8 holds every id. */
 int bpe_ids_pack_rows_device(const uint32_t* d_ids, const uint64_t* d_offsets, size_t n_rows, size_t row_len,
                              int64_t pad, int flags, int elem_bytes, void* d_out, int32_t* d_lengths,
                              void* hip_stream);
@@ -325,7 +329,9 @@ void bpe_tok_free(bpe_tokenizer* tok);
 /* Tokenizer.decode (tokenizer.py:155-157): b"".join(vocab[i] for i in ids) on the device; the
  * caller applies .decode("utf-8", errors="replace").  vocab blob: u32 count, then (i64 id,
  * u32 len, bytes) per entry -- the int-keyed entries of Tokenizer.vocab.  An id without an
- * entry fails with BPE_E_KEY (message: the id), as vocab[i] raises KeyError. */
+ * entry fails with BPE_E_KEY (message: the id), as vocab[i] raises KeyError.  Vocab ids must lie
+ * in [0, 2^28): the decoder keeps a dense table up to the largest id (the encoder takes ids up to
+ * 2^32 - 1).  One outside: BPE_E_LIMIT from bpe_dec_create. */
 typedef struct bpe_decoder bpe_decoder;
 int bpe_dec_create(const uint8_t* vocab_blob, size_t vocab_n, bpe_decoder** out);
 /* host ids -> host bytes; *n_out = byte count (also set when cap is too small: BPE_E_ARG) */

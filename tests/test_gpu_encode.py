@@ -112,7 +112,9 @@ def test_encode_several_devices_equals_one(ranks, monkeypatch):
     assert one == oracle.encode(vocab, merges, specials, text)
 
 
-@pytest.mark.parametrize("knobs", [
+# the encoder's run-time paths (the library reads these on every call; tests/test_gpu_vocab_ids.py
+# runs them too)
+RESOLUTION_KNOBS = [
     {"BPE355_ENC_PEND_CAP": "0"},                                # no pending pool: the scan resolves words
     {"BPE355_ENC_PEND_CAP": "40000", "BPE355_STREAM_WG": "2"},   # the pool runs out part way
     {"BPE355_NOCACHE": "1"},                                     # no LDS cache: every word pending
@@ -120,7 +122,10 @@ def test_encode_several_devices_equals_one(ranks, monkeypatch):
     {"BPE355_ENC_RESOLVE_CACHE": "0"},                           # the resolve without its LDS cache
     {"BPE355_ENC_FINALIZE": "0"},                                # the emit reads resolved records
     {"BPE355_ENC_FINALIZE": "2"},                                # the count pass stores the infos
-])
+]
+
+
+@pytest.mark.parametrize("knobs", RESOLUTION_KNOBS)
 def test_encode_resolution_paths(monkeypatch, knobs):
     """the encoder's record paths against the oracle: pending entries resolved by k_enc_resolve,
     words resolved in the scan itself, no LDS cache, the record buffer's retry -- with the

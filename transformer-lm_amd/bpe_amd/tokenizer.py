@@ -183,7 +183,8 @@ class Tokenizer:
         int32 lengths [len(texts)]).  T is max_length, or the longest row when it is None.  A row
         longer than T loses ids on the `truncation` side ("right": the first T are kept, "left":
         the last T); a shorter one is filled with pad_id on `padding_side`.  lengths[i] =
-        min(len(encode(texts[i])), T).  The text goes to the device once, the ids never leave it
+        min(len(encode(texts[i])), T).  With torch.int32 a kept id of 2^31 or more raises RuntimeError
+        (BPE_E_LIMIT, naming the id) instead of wrapping.  The text goes to the device once, the ids never leave it
         (bpe_tok_encode_batch_device, then bpe_ids_pack_rows_device); on the current device
         (set_num_gpus does not apply)."""
         import torch

@@ -1383,14 +1383,20 @@ __global__ void k_enc_doc_offsets(const uint32_t* __restrict__ doc_cut, size_t n
 // its first ids, or with kPackKeepLast its last; a shorter one is padded on the right, or with
 // kPackPadLeft on the left.  A thread fills one 16-byte unit of the output (kVec: row_len is a
 // multiple of the unit and the matrix is 16-byte aligned, so a unit lies in one row) or one
-// element; consecutive threads write consecutive addresses and read consecutive ids.
+// element; consecutive threads write consecutive addresses and read consecutive ids.  A kept id
+// that an int32 cannot hold (>= 2^31) is reported instead of wrapped: over[0] = 1 and over[1] =
+// the smallest such id (over[1] starts at ~0u); the int64 rows hold every id.
 constexpr int kPackKeepLast = 1, kPackPadLeft = 2;
 
 template <class OutT, bool kVec>
 __global__ void __launch_bounds__(256) k_pack_rows(const uint32_t* __restrict__ ids, const unsigned long long* __restrict__ off,
                                                    size_t n_rows, size_t row_len, OutT pad, int flags,
-                                                   OutT* __restrict__ out, int32_t* __restrict__ lengths) {
+                                                   OutT* __restrict__ out, int32_t* __restrict__ lengths,
+                                                   unsigned* __restrict__ over) {
     constexpr unsigned kPer = kVec ? 16 / sizeof(OutT) : 1;
+    constexpr bool kNarrow = sizeof(OutT) == 4;
+    uint32_t worst = 0xffffffffu;   // this thread's smallest id >= 2^31
+    bool wide = false;
     const size_t stride = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     for (size_t i = t0; i < n_rows; i += stride) {
         const unsigned long long L = off[i + 1] - off[i];
@@ -1407,7 +1413,13 @@ __global__ void __launch_bounds__(256) k_pack_rows(const uint32_t* __restrict__ 
 #pragma unroll
         for (unsigned k = 0; k < kPer; ++k) {
             const size_t cc = col + k;
-            v[k] = cc >= c0 && cc < c0 + len ? (OutT)ids[src + (cc - c0)] : pad;
+            const bool kept = cc >= c0 && cc < c0 + len;
+            const uint32_t id = kept ? ids[src + (cc - c0)] : 0u;
+            if (kNarrow && id >= 0x80000000u) {
+                wide = true;
+                worst = id < worst ? id : worst;
+            }
+            v[k] = kept ? (OutT)id : pad;
         }
         if (kVec) {
             uint4 w;
@@ -1415,6 +1427,16 @@ __global__ void __launch_bounds__(256) k_pack_rows(const uint32_t* __restrict__ 
             *reinterpret_cast<uint4*>(out + e) = w;
         } else {
             out[e] = v[0];
+        }
+    }
+    if (kNarrow && __ballot(wide)) {   // (every thread of the wave is here: no early return above)
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t w = __shfl_xor(worst, o);
+            worst = w < worst ? w : worst;
+        }
+        if ((threadIdx.x & 63) == 0) {
+            atomicOr(&over[0], 1u);
+            atomicMin(&over[1], worst);
         }
     }
 }
@@ -2708,14 +2730,23 @@ int bpe_ids_pack_rows_device(const uint32_t* d_ids, const uint64_t* d_offsets, s
         const unsigned grid = bpe::grid_for(std::max(n_rows, n_rows * row_len / (vec ? per : 1)), 256);
         const unsigned long long* off = reinterpret_cast<const unsigned long long*>(d_offsets);
         if (elem_bytes == 4) {
+            bpe::DevBuf<unsigned> over(2);   // {an id >= 2^31 was kept, the smallest such id}
+            const unsigned init[2] = {0u, 0xffffffffu};
+            unsigned got[2] = {0u, 0u};
+            BPE_HIP(hipMemcpyAsync(over.p, init, sizeof(init), hipMemcpyHostToDevice, s));
             auto k = vec ? bpe::k_pack_rows<int32_t, true> : bpe::k_pack_rows<int32_t, false>;
             hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, s, d_ids, off, n_rows, row_len, (int32_t)pad, flags,
-                               static_cast<int32_t*>(d_out), d_lengths);
-        } else {
-            auto k = vec ? bpe::k_pack_rows<int64_t, true> : bpe::k_pack_rows<int64_t, false>;
-            hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, s, d_ids, off, n_rows, row_len, pad, flags,
-                               static_cast<int64_t*>(d_out), d_lengths);
+                               static_cast<int32_t*>(d_out), d_lengths, over.p);
+            BPE_HIP(hipGetLastError());
+            BPE_HIP(hipMemcpyAsync(got, over.p, sizeof(got), hipMemcpyDeviceToHost, s));
+            BPE_HIP(hipStreamSynchronize(s));
+            BPE_REQUIRE(!got[0], BPE_E_LIMIT, "token id " + std::to_string(got[1]) +
+                                                  " does not fit int32 rows (ids from 2^31 on need elem_bytes 8)");
+            return;
         }
+        auto k = vec ? bpe::k_pack_rows<int64_t, true> : bpe::k_pack_rows<int64_t, false>;
+        hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, s, d_ids, off, n_rows, row_len, pad, flags,
+                           static_cast<int64_t*>(d_out), d_lengths, static_cast<unsigned*>(nullptr));
         BPE_HIP(hipGetLastError());
         BPE_HIP(hipStreamSynchronize(s));
     });
