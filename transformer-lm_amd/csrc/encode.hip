@@ -44,6 +44,7 @@
 #include <string>
 #include <thread>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "drive.h"
@@ -1713,9 +1714,10 @@ void build_tokenizer(bpe_tokenizer& T, const uint8_t* vb, size_t vn, const uint8
         p += l;
     }
     // specials: dedupe (first occurrence), longest first; missing ones get ids len(vocab), ...
+    std::unordered_set<std::string> seen_sp;   // (a linear search per special: seconds at the 65 535 limit)
     for (const auto& s : sp_in) {
         BPE_REQUIRE(!s.empty(), BPE_E_ARG, "empty special token is not supported");
-        if (std::find(T.specials.begin(), T.specials.end(), s) == T.specials.end()) T.specials.push_back(s);
+        if (seen_sp.insert(s).second) T.specials.push_back(s);
     }
     std::stable_sort(T.specials.begin(), T.specials.end(),
                      [](const std::string& x, const std::string& y) { return x.size() > y.size(); });
