@@ -1,9 +1,12 @@
 // Host evaluation of the byte-parallel token-start predicate (tokstart.h), block by block exactly
 // as the device counter evaluates it, for the CPU tests that check it against the serial scanner
-// and the oracle (tests/test_tokstart.py).  Test support: no product path calls it.
+// and the oracle (tests/test_tokstart.py); and the word hash of stage.h on the host, for the CPU
+// test that ties the counter's constructed inputs to it (tests/test_count_cases.py).  Test support:
+// no product path calls either.
 #include <cstring>
 
 #include "internal.h"
+#include "stage.h"
 #include "tokstart.h"
 
 namespace bpe {
@@ -43,6 +46,22 @@ extern "C" int bpe_pretok_starts_host(const uint8_t* text, size_t n, uint8_t* fl
         uint64_t m = bpe::token_starts64<bpe::hosttab::Tab>(HostWin{w}, (int)(vhi > bpe::kStartWin ? bpe::kStartWin : vhi));
         if (o == 0) m |= 1;   // the text start
         for (int k = 0; k < 64 && o + k < n; ++k) flags[o + k] = (uint8_t)((m >> k) & 1);
+    }
+    return BPE_OK;
+}
+
+// out[i] = short_hash of word i of `n` words of `len` bytes each (2..16), laid end to end: the
+// packing is pack_word's (byte i of the word is bits 8 i of lo for i < 8, of hi beyond)
+extern "C" int bpe_short_hash_host(const uint8_t* words, size_t n, size_t len, uint64_t* out) {
+    if ((!words && n) || (!out && n) || len < 2 || len > (size_t)bpe::kInline) return BPE_E_ARG;
+    for (size_t w = 0; w < n; ++w) {
+        uint64_t lo = 0, hi = 0;
+        for (size_t i = 0; i < len; ++i) {
+            const uint64_t b = words[w * len + i];
+            if (i < 8) lo |= b << (8 * i);
+            else hi |= b << (8 * (i - 8));
+        }
+        out[w] = bpe::short_hash(lo, hi, len);
     }
     return BPE_OK;
 }
