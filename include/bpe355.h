@@ -314,6 +314,77 @@ int bpe_ids_pack_rows_device(const uint32_t* d_ids, const uint64_t* d_offsets, s
  * piece starts, of the encodes and of the copy to host. */
 int bpe_tok_encode_file_u16(bpe_tokenizer* tok, const char* path, size_t chars_per_piece, uint16_t* ids_out,
                             size_t cap, size_t* n_out, double* phase_ms);
+/* The dataset encoder over many files of any size: every file is encoded exactly as
+ * bpe_tok_encode_file_u16 encodes it alone (text-mode read, pieces of chars_per_piece characters of
+ * the translated text counted from the start of that file, each piece on its own), the files' ids
+ * are concatenated in the order of paths and written to out_path as raw little-endian ids of
+ * id_bytes each (what np.memmap(path, dtype) reads).
+ *
+ * Read grid and carry: the raw bytes of each file are read in consecutive ranges of exactly
+ * window_bytes (0: 1 GiB, a choice and not a measured optimum; else at least 65536), the last
+ * range shorter.  What a range cannot finish waits for the next one: bpe_window_holdback bytes of
+ * its end (an incomplete UTF-8 character, a final \r that may be half of \r\n), and, of the
+ * translated text, the bytes after the last piece start found (a window edge is not a piece edge).
+ * A piece longer than a window grows the text buffer for that piece only (stats->n_grows).
+ *
+ * Memory.  Device: two raw read buffers of window_bytes + 32; one translated-text buffer of the
+ * carry (less than one piece) + window_bytes + 64; two id buffers of id_bytes per byte of that
+ * text buffer; while a window that holds a \r is translated, three more arrays of its size; the
+ * separator positions of one region (8 bytes per match, at least 64 KiB); the n_counts table; on
+ * top of the encoder's per-call arrays for one region.  stats->device_bytes is what this call's
+ * buffers held at most.  The buffers stay with the tokenizer until bpe_tok_release_buffers.  Host:
+ * the ids of one region.  Nothing grows with a file's or the corpus' size.  Input that is not a
+ * regular file (a FIFO) is read to its end into host memory first.
+ *
+ * opts->has_separator: the positions p of the whole output stream with ids[p] == separator_id go
+ * to index_path, ascending, as raw little-endian uint64 (index_path is required then, and must be
+ * NULL otherwise).  id_counts (NULL, or n_counts entries in host memory): set to the occurrences of
+ * every id, accumulated on the device in 64 bits; an emitted id at or above n_counts is BPE_E_ARG.
+ * file_id_offsets (NULL or n_paths + 1 entries): file i's ids are [offsets[i], offsets[i + 1]).
+ *
+ * Errors: a file that cannot be opened or read is BPE_E_IO with errno; ill-formed UTF-8 is
+ * BPE_E_UTF8 whose message gives the byte's position in that raw file and the file's name; an id
+ * that does not fit id_bytes == 2 is BPE_E_LIMIT, never a wrapped id.  Both outputs are written
+ * under a temporary name beside their path and renamed when the whole call has succeeded: after
+ * an error out_path and index_path are as they were, absent or the old file untouched.
+ * The stages overlap: a reader thread fills the next raw buffer and a writer thread copies out and
+ * pwrites the previous region's ids while the current one is decoded and encoded.  Runs on the
+ * current device; one call at a time per tokenizer. */
+typedef struct bpe_dataset_opts {
+    size_t chars_per_piece;   /* > 0 */
+    size_t window_bytes;      /* 0: the 1 GiB default */
+    int id_bytes;             /* 2 (uint16) or 4 (uint32) */
+    int has_separator;
+    uint64_t separator_id;
+    const char* index_path;
+} bpe_dataset_opts;
+typedef struct bpe_dataset_stats {
+    uint64_t n_ids, n_bytes, n_pieces, n_windows, max_window_bytes, n_separators, device_bytes, n_grows;
+    /* busy milliseconds (they overlap): the reader; validation, newlines and piece starts; the
+     * encodes; the copy-out and pwrite; the histogram and the separator search */
+    double read_ms, decode_ms, encode_ms, write_ms, stats_ms;
+} bpe_dataset_stats;
+int bpe_tok_encode_files(bpe_tokenizer* tok, const char* const* paths, size_t n_paths, const char* out_path,
+                         const bpe_dataset_opts* opts, uint64_t* file_id_offsets, uint64_t* id_counts,
+                         size_t n_counts, bpe_dataset_stats* stats);
+/* How many of the last n (at most the last 4 are looked at) raw bytes of a read range must wait
+ * for the next range: the longest suffix that is a proper prefix of a well-formed UTF-8 sequence,
+ * else 1 for a final \r (it may be the first half of \r\n), else 0; always 0 with at_eof.  Host
+ * only; the dataset encoder's carry uses this very function. */
+size_t bpe_window_holdback(const uint8_t* tail, size_t n, int at_eof);
+/* d_counts[id] += occurrences of id in d_ids[0, n), 64-bit (the table accumulates over calls).
+ * d_ids: ids of elem_bytes 2, 4 or 8 (unsigned; an 8-byte id must lie in [0, 2^32)) in device
+ * memory, aligned to elem_bytes only; d_counts: n_counts <= 2^32 uint64 in device memory.  An id
+ * at or above n_counts is BPE_E_ARG with the smallest such id in the message, and the table is
+ * then not to be used.  Frequent ids below 8192 are counted in LDS per workgroup and flushed with
+ * 64-bit adds.  Returns once the table is updated. */
+int bpe_ids_histogram_device(const void* d_ids, size_t n, int elem_bytes, uint64_t* d_counts, size_t n_counts,
+                             void* hip_stream);
+/* base + i for every i with d_ids[i] == value, ascending, into d_pos_out (device, cap entries);
+ * *n_out = how many there are, which may exceed cap (then only the first cap were written: call
+ * again with room for all).  d_ids as above.  Returns once the positions are written. */
+int bpe_ids_find_device(const void* d_ids, size_t n, int elem_bytes, uint64_t value, uint64_t base,
+                        uint64_t* d_pos_out, size_t cap, size_t* n_out, void* hip_stream);
 /* encode(text) on n_gpus devices of this process (<= 0: every visible one; SURVEY.md 8b's n_gpus):
  * the text is cut at safe split points that no special token spans, each device encodes its
  * piece, the ids are concatenated -- identical to bpe_tok_encode (tokenizer.py:111-138). */

@@ -10,3 +10,12 @@ from .train import (train_bpe, train_bpe_bytes, train_bpe_device, last_train_sta
 from .counter import WordCounter, train_bpe_files, train_bpe_word_counts  # noqa: F401
 from .vocab import Vocab  # noqa: F401
 from .tokenizer import Tokenizer  # noqa: F401
+
+
+def __getattr__(name):
+    # encode_files, id_counts, id_positions live in bpe_amd.encode, which is also run as a script
+    # (python -m bpe_amd.encode): imported on first use, not with the package
+    if name in ("encode_files", "id_counts", "id_positions"):
+        from . import encode
+        return getattr(encode, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -62,7 +62,23 @@ class CounterInfo(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
-HOST_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p,
+class DatasetOpts(ctypes.Structure):
+    _fields_ = [("chars_per_piece", ctypes.c_size_t), ("window_bytes", ctypes.c_size_t),
+                ("id_bytes", ctypes.c_int), ("has_separator", ctypes.c_int),
+                ("separator_id", ctypes.c_uint64), ("index_path", ctypes.c_char_p)]
+
+
+class DatasetStats(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in (
+        "n_ids", "n_bytes", "n_pieces", "n_windows", "max_window_bytes", "n_separators", "device_bytes",
+        "n_grows")] + [(name, ctypes.c_double) for name in (
+            "read_ms", "decode_ms", "encode_ms", "write_ms", "stats_ms")]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+HOST_ALLREDUCE_FN =ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p,
                                      ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t)
 
 _lib = None
@@ -137,6 +153,13 @@ _SIGS = [
                                                 _P, _P, _P]),
     ("bpe_tok_encode_file_u16", ctypes.c_int, [_P, ctypes.c_char_p, _SZ, _P, _SZ, ctypes.POINTER(_SZ),
                                                ctypes.POINTER(ctypes.c_double)]),
+    ("bpe_tok_encode_files", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_char_p), _SZ, ctypes.c_char_p,
+                                            ctypes.POINTER(DatasetOpts), _P, _P, _SZ,
+                                            ctypes.POINTER(DatasetStats)]),
+    ("bpe_window_holdback", _SZ, [_U8P, _SZ, ctypes.c_int]),
+    ("bpe_ids_histogram_device", ctypes.c_int, [_P, _SZ, ctypes.c_int, _P, _SZ, _P]),
+    ("bpe_ids_find_device", ctypes.c_int, [_P, _SZ, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, _P, _SZ,
+                                           ctypes.POINTER(_SZ), _P]),
     ("bpe_tok_release_buffers", ctypes.c_int, [_P]),
     ("bpe_tok_free", None, [_P]),
     ("bpe_dec_create", ctypes.c_int, [_U8P, _SZ, ctypes.POINTER(_P)]),

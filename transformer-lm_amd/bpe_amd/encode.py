@@ -150,6 +150,177 @@ def encode_file(tokenizer: Tokenizer, input_path, output_path=None, fmt: str = "
     return pt
 
 
+MIN_WINDOW_BYTES = 64 * 1024    # as WordCounter.add_file
+DEFAULT_WINDOW_BYTES = 1 << 30  # a choice, not a measured optimum
+
+
+def _largest_id(tokenizer: Tokenizer) -> int:
+    """The largest id the tokenizer can emit: a vocab entry's or a special's."""
+    ids = [i for b, i in tokenizer.vocab_inv.items() if isinstance(b, (bytes, bytearray)) and isinstance(i, int)]
+    return max(ids) if ids else 0
+
+
+def _same_file(a, b) -> bool:
+    a, b = os.fspath(a), os.fspath(b)
+    if os.path.realpath(a) == os.path.realpath(b):
+        return True
+    try:
+        return os.path.samefile(a, b)
+    except OSError:
+        return False
+
+
+def encode_files(tokenizer: Tokenizer, paths, output_path, *, dtype=None, window_bytes=None,
+                 chars_per_piece: int = CHARS_PER_PIECE, separator=None, index_path=None,
+                 count_ids: bool = False, keep_device_buffers: bool = False) -> dict:
+    """Encode many text files of any size into one token file.
+
+    Each file is encoded exactly as encode_file encodes it alone (text-mode read, pieces of
+    chars_per_piece characters counted from the start of that file, each piece on its own); the
+    ids are concatenated in the order of `paths` and written to output_path as raw little-endian
+    ids, what np.memmap(output_path, dtype) reads.  The raw bytes of each file are read in
+    consecutive ranges of exactly window_bytes (None: 1 GiB; at least 64 KiB); neither HBM nor
+    host memory holds anything proportional to a file's size (the exact bound: include/bpe355.h,
+    bpe_tok_encode_files).  Input that is not a regular file (a FIFO) is read to its end into
+    host memory first, as encode_file does.
+
+    dtype: np.uint16 or np.uint32; None picks uint16 when every id the tokenizer can emit is below
+    65536, else uint32.  A forced uint16 with a wider id raises RuntimeError (BPE_E_LIMIT).
+    separator (a special-token string of the tokenizer, or an int id) with index_path: the
+    positions in the whole stream where that id stands, ascending, raw little-endian uint64.
+    count_ids: the result carries id_counts, np.uint64 of length largest emittable id + 1,
+    accumulated on the device.
+
+    Raises FileNotFoundError for a missing file and UnicodeDecodeError (position in that raw file,
+    the message names the file) for ill-formed UTF-8; after any error output_path and index_path
+    are as they were before the call.  Runs on the current device (set_num_gpus does not apply).
+    The device buffers are released afterwards unless keep_device_buffers.
+
+    Returns a dict: n_ids, dtype, file_offsets (np.int64, len(paths) + 1), n_bytes, n_pieces,
+    n_windows, max_window_bytes, n_separators, n_grows, device_bytes, the busy milliseconds
+    read_ms, decode_ms, encode_ms, write_ms and stats_ms, and id_counts when asked for."""
+    paths = [os.fspath(p) for p in paths]
+    if dtype is not None:
+        try:
+            dtype = np.dtype(dtype)
+        except TypeError as e:
+            raise ValueError(f"dtype must be np.uint16 or np.uint32, not {dtype!r}") from e
+        if dtype not in (np.dtype(np.uint16), np.dtype(np.uint32)):
+            raise ValueError(f"dtype must be np.uint16 or np.uint32, not {dtype}")
+    if window_bytes is not None and int(window_bytes) < MIN_WINDOW_BYTES:
+        raise ValueError(f"window_bytes must be at least {MIN_WINDOW_BYTES}")
+    if int(chars_per_piece) < 1:
+        raise ValueError("chars_per_piece must be at least 1")
+    if (separator is None) != (index_path is None):
+        raise ValueError("separator and index_path go together")
+    sep_id = 0
+    if separator is not None:
+        if isinstance(separator, str):
+            if separator not in tokenizer.special_tokens:
+                raise ValueError(f"{separator!r} is not a special token of the tokenizer")
+            sep_id = tokenizer.vocab_inv[separator.encode("utf-8")]
+        else:
+            sep_id = int(separator)
+            if sep_id < 0:
+                raise ValueError("a separator id is not negative")
+    outs = [output_path] + ([index_path] if index_path is not None else [])
+    if index_path is not None and _same_file(output_path, index_path):
+        raise ValueError("output_path and index_path are the same file")
+    for o in outs:
+        for p in paths:
+            if _same_file(o, p):
+                raise ValueError(f"{os.fspath(o)!r} is both an input and an output")
+    for p in paths:
+        os.stat(p)   # missing: FileNotFoundError, as open() raises, before the device is touched
+    top = _largest_id(tokenizer)
+    if dtype is None:
+        dtype = np.dtype(np.uint16 if top < 65536 else np.uint32)
+
+    L = _lib.lib()
+    opts = _lib.DatasetOpts(int(chars_per_piece), int(window_bytes or 0), dtype.itemsize,
+                            1 if separator is not None else 0, sep_id,
+                            os.fsencode(os.fspath(index_path)) if index_path is not None else None)
+    arr = (ctypes.c_char_p * max(1, len(paths)))(*[os.fsencode(p) for p in paths])
+    offsets = np.zeros(len(paths) + 1, dtype=np.uint64)
+    counts = np.zeros(top + 1, dtype=np.uint64) if count_ids else None
+    st = _lib.DatasetStats()
+    try:
+        rc = L.bpe_tok_encode_files(tokenizer._device(), arr, len(paths), os.fsencode(os.fspath(output_path)),
+                                    ctypes.byref(opts), offsets.ctypes.data,
+                                    counts.ctypes.data if count_ids else None, counts.size if count_ids else 0,
+                                    ctypes.byref(st))
+        _lib.check(rc, "encode files")
+    finally:
+        if not keep_device_buffers:
+            tokenizer.release_device_buffers()
+    out = st.as_dict()
+    out["dtype"] = dtype
+    out["file_offsets"] = offsets.astype(np.int64)
+    if count_ids:
+        out["id_counts"] = counts
+    return out
+
+
+def _ids_arg(ids):
+    import torch
+    sizes = {torch.int16: 2, torch.uint16: 2, torch.int32: 4, torch.int64: 8}
+    if not (isinstance(ids, torch.Tensor) and ids.is_cuda and ids.dim() == 1 and ids.is_contiguous()
+            and ids.dtype in sizes):
+        raise ValueError("ids must be a contiguous 1-D cuda tensor of int16, uint16, int32 or int64")
+    return sizes[ids.dtype]
+
+
+def _check_ids(rc: int, what: str):
+    if rc == _lib.BPE_E_ARG:   # an id outside the table or outside [0, 2^32)
+        raise ValueError((_lib.lib().bpe_last_error() or b"").decode("utf-8", "replace"))
+    _lib.check(rc, what)
+
+
+def id_counts(ids, size: int, out=None):
+    """out[id] += occurrences of id in `ids` (a contiguous 1-D cuda tensor of int16/uint16, int32 or
+    int64; the bits of int16 and int32 are read as unsigned, an int64 entry outside [0, 2^32) is an
+    error), as a uint64 tensor of `size` entries on the device (out: such a tensor to add into,
+    uint64 or int64 bits; None: zeros).  An id >= size raises ValueError naming the smallest one,
+    and `out` is not to be used after that."""
+    import torch
+    eb = _ids_arg(ids)
+    size = int(size)
+    if size < 1 or size > 1 << 32:
+        raise ValueError("size must be in [1, 2^32]")
+    if out is None:
+        out = torch.zeros(size, dtype=torch.int64, device=ids.device).view(torch.uint64)
+    elif not (isinstance(out, torch.Tensor) and out.device == ids.device and out.dim() == 1 and out.is_contiguous()
+              and out.numel() == size and out.dtype in (torch.uint64, torch.int64)):
+        raise ValueError("out must be a contiguous uint64 cuda tensor of `size` entries beside ids")
+    with torch.cuda.device(ids.device):
+        torch.cuda.current_stream().synchronize()
+        _check_ids(_lib.lib().bpe_ids_histogram_device(ctypes.c_void_p(ids.data_ptr()), ids.numel(), eb,
+                                                       ctypes.c_void_p(out.data_ptr()), size, None), "id counts")
+    return out
+
+
+def id_positions(ids, value: int, base: int = 0):
+    """base + i for every i with ids[i] == value, ascending, as an int64 tensor on the device
+    (ids as for id_counts)."""
+    import torch
+    eb = _ids_arg(ids)
+    value, base = int(value), int(base)
+    if value < 0 or base < 0:
+        raise ValueError("value and base are not negative")
+    L = _lib.lib()
+    n = ctypes.c_size_t(0)
+    with torch.cuda.device(ids.device):
+        torch.cuda.current_stream().synchronize()
+        _check_ids(L.bpe_ids_find_device(ctypes.c_void_p(ids.data_ptr()), ids.numel(), eb, value, base, None, 0,
+                                         ctypes.byref(n), None), "id positions")
+        pos = torch.empty(n.value, dtype=torch.int64, device=ids.device)
+        if n.value:
+            _check_ids(L.bpe_ids_find_device(ctypes.c_void_p(ids.data_ptr()), ids.numel(), eb, value, base,
+                                             ctypes.c_void_p(pos.data_ptr()), n.value, ctypes.byref(n), None),
+                       "id positions")
+    return pos
+
+
 def main(dataset: str, split: str, fmt: str = "pt"):
     """encode.py:18-38 with the same paths."""
     if dataset == "corpus":

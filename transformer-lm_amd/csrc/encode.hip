@@ -47,6 +47,9 @@
 #include <unordered_set>
 #include <vector>
 
+#include <fcntl.h>
+#include <unistd.h>
+
 #include "drive.h"
 #include "internal.h"
 #include "prims.h"
@@ -1543,6 +1546,14 @@ struct bpe_tokenizer {
         // encode_batch: per chunk its first cut, per cut its record index and id offset, per document its cut
         bpe::DevBuf<uint32_t> chunk_cut0, cut_rec, doc_cut;
         bpe::DevBuf<unsigned long long> cut_off;
+        // the dataset encoder (encode_files_pipelined): the raw read ring, the translated text and
+        // the buffer its carry moves through, the id ring, one region's separator positions, the
+        // id table
+        struct Dataset {
+            bpe::DevBuf<uint8_t> raw[2], text, move, ids[2];
+            bpe::DevBuf<unsigned long long> pos, counts;
+            bpe::IdScratch stat;
+        } ds;
     } sc;
     // construction inputs, to build the same tables for the other ranks of a multi-device encode
     // (bpe_tok_encode_gpus); those copies own their stream and record buffer
@@ -2566,6 +2577,360 @@ size_t encode_file_pipelined(bpe_tokenizer& T, const Source& src, size_t K, uint
     return kk;
 }
 
+// ------------------------------------------------------------------ many files -> one token file
+// The dataset encoder (bpe_tok_encode_files): encode_file's result for every file, concatenated,
+// without holding anything proportional to a file in HBM or in host memory.
+//
+// Read grid.  A reader thread reads each file's raw bytes in consecutive ranges of exactly W =
+// window_bytes (the last one shorter) into a ring of two raw buffers, one range ahead of the
+// main thread.  Carry.  Of a range's end, bpe_window_holdback bytes (an incomplete UTF-8
+// character, a final \r that may be half of \r\n) wait and are put in front of the next range,
+// so every range that is decoded ends on a character and never inside \r\n: prepare_text on it
+// gives exactly the bytes the text-mode read of the whole file gives for it, and its error
+// position plus the range's file offset is the position in the file.  The translated bytes are
+// appended to the text buffer behind the carried text; piece_starts_range, with the file's
+// running character count, finds the piece starts among the new bytes.  Everything before the
+// last piece start is a run of whole pieces and is encoded with the starts as cuts; the bytes from
+// that start on are the next buffer's carry, moved to the front device to device (at the end of
+// the file everything is encoded).  A window edge is thus never a piece edge, and a special token
+// that spans one is matched like any other.  With no piece start in the buffer the whole buffer
+// is carried and the buffer grows by one window: a piece longer than a window.
+//
+// Device memory of the call (bpe_dataset_stats.device_bytes reports the sum): 2 raw buffers of
+// W + 32; the text buffer of carry + W + 64, carry < the bytes of one piece; its carry moves
+// through a second buffer of at most the carry only when source and destination overlap; 2 id
+// buffers of sizeof(OutT) x the text buffer's size; 8 MiB of separator positions; the id table;
+// while a window with a \r is translated, prepare_text's three arrays of its size.
+//
+// A writer thread copies each region's ids to the host and pwrites them at their stream offset
+// while the next region is decoded and encoded (the id ring has two buffers for that).  The
+// histogram and the separator search run on the region's ids right after its emit.
+constexpr size_t kDatasetWindow = 1ull << 30;
+constexpr size_t kRawSlack = 16;            // in front of a raw buffer: the held-back bytes go there
+constexpr size_t kDatasetPosCap = 1u << 20; // separator positions one search returns at most
+
+void pwrite_all(int fd, const void* p, size_t n, uint64_t off, const std::string& what) {
+    const uint8_t* b = static_cast<const uint8_t*>(p);
+    size_t done = 0;
+    while (done < n) {
+        const ssize_t r = ::pwrite(fd, b + done, n - done, (off_t)(off + done));
+        if (r < 0) {
+            if (errno == EINTR) continue;
+            throw Error{BPE_E_IO, "cannot write " + what, errno};
+        }
+        done += (size_t)r;
+    }
+}
+
+template <class OutT>
+void encode_files_pipelined(bpe_tokenizer& T, const char* const* paths, size_t n_paths, int out_fd, int idx_fd,
+                            const bpe_dataset_opts& O, uint64_t* file_off, uint64_t* counts, size_t n_counts,
+                            bpe_dataset_stats& st, int dev) {
+    using clk = std::chrono::steady_clock;
+    auto since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
+    auto& S = T.sc;
+    auto& D = T.sc.ds;
+    const hipStream_t s = T.stream;
+    const size_t K = O.chars_per_piece;
+    const size_t W = O.window_bytes ? O.window_bytes : kDatasetWindow;
+    const int io_n = (int)env_size("BPE355_ENC_IO_THREADS", 8);
+    const int copy_n = (int)env_size("BPE355_ENC_COPY_THREADS", 4);
+    // test knob: a small position buffer, so that a dense region is searched in several parts
+    const size_t pos_cap = std::max<size_t>(16, env_size("BPE355_DS_POS_CAP", kDatasetPosCap));
+    for (auto& r : D.raw) r.reserve(W + 2 * kRawSlack);
+    D.text.reserve(W + 64);
+    if (O.has_separator) D.pos.reserve(pos_cap);
+    if (counts) {
+        D.counts.reserve(n_counts);
+        BPE_HIP(hipMemsetAsync(D.counts.p, 0, n_counts * 8, s));
+    }
+
+    // ---- reader: one range ahead
+    struct Win {
+        size_t file = 0, off = 0, len = 0;
+        bool eof = false;
+        uint8_t tail[4] = {0, 0, 0, 0};
+        unsigned tail_n = 0;
+        int slot = -1;
+    };
+    std::mutex m;
+    std::condition_variable cv;
+    std::deque<Win> ready;
+    bool raw_free[2] = {true, true};
+    bool read_done = false;
+    std::atomic<bool> stop{false};
+    std::exception_ptr read_err;
+    double read_ms = 0;
+    std::thread reader([&] {
+        double busy = 0;
+        try {
+            size_t seq = 0;
+            for (size_t f = 0; f < n_paths && !stop.load(); ++f) {
+                const Source src = Source::open_path(paths[f]);
+                if (src.size == 0) {   // no ids; the main thread closes the file's id range
+                    Win w;
+                    w.file = f;
+                    w.eof = true;
+                    std::lock_guard<std::mutex> g(m);
+                    ready.push_back(w);
+                    cv.notify_all();
+                    continue;
+                }
+                for (size_t off = 0; off < src.size && !stop.load(); off += W) {
+                    Win w;
+                    w.file = f;
+                    w.off = off;
+                    w.len = std::min(W, src.size - off);
+                    w.eof = off + w.len == src.size;
+                    w.slot = (int)(seq++ & 1);
+                    {
+                        std::unique_lock<std::mutex> g(m);
+                        cv.wait(g, [&] { return raw_free[w.slot] || stop.load(); });
+                        if (stop.load()) break;
+                        raw_free[w.slot] = false;
+                    }
+                    const auto t0 = clk::now();
+                    stage_to_device(src, off, w.len, D.raw[w.slot].p + kRawSlack, dev, io_n);
+                    w.tail_n = (unsigned)std::min<size_t>(4, w.len);
+                    src.read(off + w.len - w.tail_n, w.tail_n, w.tail);
+                    busy += since(t0);
+                    std::lock_guard<std::mutex> g(m);
+                    ready.push_back(w);
+                    cv.notify_all();
+                }
+            }
+        } catch (...) {
+            std::lock_guard<std::mutex> g(m);
+            read_err = std::current_exception();
+        }
+        std::lock_guard<std::mutex> g(m);
+        read_ms = busy;
+        read_done = true;
+        cv.notify_all();
+    });
+
+    // ---- writer: ids of a region -> host -> the output file at their stream offset
+    struct Job { int slot; size_t count; uint64_t at; };
+    std::mutex qm;
+    std::condition_variable qcv;
+    std::deque<Job> jobs;
+    bool ids_free[2] = {true, true};
+    bool jobs_closed = false;
+    std::exception_ptr write_err;
+    double write_ms = 0;
+    std::thread writer([&] {
+        std::vector<uint8_t> host;
+        for (;;) {
+            Job j;
+            {
+                std::unique_lock<std::mutex> g(qm);
+                qcv.wait(g, [&] { return !jobs.empty() || jobs_closed; });
+                if (jobs.empty()) return;
+                j = jobs.front();
+                jobs.pop_front();
+            }
+            const auto t0 = clk::now();
+            bool failed;
+            {
+                std::lock_guard<std::mutex> g(qm);
+                failed = (bool)write_err;
+            }
+            if (!failed && !stop.load()) {
+                try {
+                    const size_t bytes = j.count * sizeof(OutT);
+                    if (host.size() < bytes) host.resize(bytes);
+                    device_to_host(D.ids[j.slot].p, bytes, host.data(), dev, copy_n);
+                    pwrite_all(out_fd, host.data(), bytes, j.at * sizeof(OutT), "the token file");
+                } catch (...) {
+                    std::lock_guard<std::mutex> g(qm);
+                    write_err = std::current_exception();
+                }
+            }
+            std::lock_guard<std::mutex> g(qm);
+            write_ms += since(t0);
+            ids_free[j.slot] = true;
+            qcv.notify_all();
+        }
+    });
+    auto join_all = [&] {
+        stop.store(true);
+        {
+            std::lock_guard<std::mutex> g(m);
+            cv.notify_all();
+        }
+        if (reader.joinable()) reader.join();
+        {
+            std::lock_guard<std::mutex> g(qm);
+            jobs_closed = true;
+        }
+        qcv.notify_all();
+        if (writer.joinable()) writer.join();
+    };
+
+    uint64_t k_done = 0, n_sep = 0;
+    try {
+        size_t carry = 0;          // translated bytes at the front of the text buffer
+        uint64_t chars = 0;        // characters of the current file before the bytes not yet counted
+        unsigned hold_prev = 0;    // raw bytes held back from the previous range
+        uint8_t held[4] = {0, 0, 0, 0};
+        int id_slot = 0;
+        std::vector<uint64_t> starts;
+        std::vector<unsigned long long> hpos;
+        if (file_off) file_off[0] = 0;
+        for (;;) {
+            Win w;
+            {
+                std::unique_lock<std::mutex> g(m);
+                cv.wait(g, [&] { return !ready.empty() || read_done; });
+                if (ready.empty()) {
+                    if (read_err) std::rethrow_exception(read_err);
+                    break;
+                }
+                w = ready.front();
+                ready.pop_front();
+            }
+            size_t total = carry;
+            if (w.len) {
+                ++st.n_windows;
+                st.n_bytes += w.len;
+                st.max_window_bytes = std::max<uint64_t>(st.max_window_bytes, w.len);
+                const auto t1 = clk::now();
+                const unsigned hold = (unsigned)bpe_window_holdback(w.tail, w.tail_n, w.eof ? 1 : 0);
+                uint8_t* const in = D.raw[w.slot].p + kRawSlack - hold_prev;
+                if (hold_prev) to_device(in, held, hold_prev, s);
+                const size_t nin = hold_prev + w.len - hold;
+                size_t mlen = 0;
+                DevBuf<uint8_t> nl;   // the translated copy of a window that holds a \r
+                const uint8_t* t = nullptr;
+                try {
+                    t = prepare_text(in, nin, nl, &mlen, s);
+                } catch (const Error& e) {
+                    const size_t p = e.msg.find("position ");
+                    if (e.code != BPE_E_UTF8 || p == std::string::npos) throw;
+                    throw Error{BPE_E_UTF8, "'utf-8' codec can't decode byte at position " +
+                                                std::to_string(std::stoull(e.msg.substr(p + 9)) + (w.off - hold_prev)) +
+                                                " of " + paths[w.file]};
+                }
+                if (D.text.n < carry + mlen + 64) {   // a piece longer than the buffer: grow, keep the carry
+                    DevBuf<uint8_t> nb(carry + mlen + 64);
+                    if (carry) BPE_HIP(hipMemcpyAsync(nb.p, D.text.p, carry, hipMemcpyDeviceToDevice, s));
+                    BPE_HIP(hipStreamSynchronize(s));
+                    D.text = std::move(nb);
+                    ++st.n_grows;
+                }
+                BPE_HIP(hipMemcpyAsync(D.text.p + carry, t, mlen, hipMemcpyDeviceToDevice, s));
+                starts.clear();
+                chars += piece_starts_range(D.text.p + carry, mlen, K, chars, carry, s, starts, &S.piece);
+                BPE_HIP(hipStreamSynchronize(s));   // the raw buffer has been copied out of
+                nl.release();
+                {
+                    std::lock_guard<std::mutex> g(m);
+                    raw_free[w.slot] = true;
+                    cv.notify_all();
+                }
+                hold_prev = hold;
+                for (unsigned i = 0; i < hold; ++i) held[i] = w.tail[w.tail_n - hold + i];
+                total = carry + mlen;
+                st.decode_ms += since(t1);
+            }
+            // whole pieces: up to the last piece start in the buffer, or to the end of the file
+            const size_t e_end = w.eof ? total : (starts.empty() || !w.len ? 0 : (size_t)starts.back());
+            if (e_end) {
+                std::vector<unsigned long long> cuts;
+                for (const uint64_t c : starts)
+                    if (c > 0 && c < e_end) cuts.push_back(c);
+                {
+                    std::unique_lock<std::mutex> g(qm);
+                    qcv.wait(g, [&] { return ids_free[id_slot] || (bool)write_err; });
+                    if (write_err) std::rethrow_exception(write_err);
+                    ids_free[id_slot] = false;
+                }
+                struct SlotGuard {   // an encode that throws gives the slot back
+                    std::mutex& qm; bool& flag; bool armed = true;
+                    ~SlotGuard() { if (armed) { std::lock_guard<std::mutex> g(qm); flag = true; } }
+                } guard{qm, ids_free[id_slot]};
+                D.ids[id_slot].reserve(e_end * sizeof(OutT) + 64);
+                OutT* const ids = reinterpret_cast<OutT*>(D.ids[id_slot].p);
+                const auto t2 = clk::now();
+                const size_t kk = encode_device(T, D.text.p, e_end, ids, s, cuts);
+                st.encode_ms += since(t2);
+                st.n_pieces += cuts.size() + 1;
+                const auto t3 = clk::now();
+                if (counts) ids_histogram(ids, kk, (int)sizeof(OutT), D.counts.p, n_counts, s, D.stat);
+                if (O.has_separator) {
+                    // a part of at most pos_cap ids has at most pos_cap matches: the whole region
+                    // in one search when its matches fit, else part by part
+                    size_t found = ids_find(ids, kk, (int)sizeof(OutT), O.separator_id, k_done, D.pos.p, pos_cap, s, D.stat);
+                    auto flush_pos = [&](size_t cnt) {
+                        if (!cnt) return;
+                        hpos.resize(cnt);
+                        to_host(hpos.data(), D.pos.p, cnt * 8, s);
+                        pwrite_all(idx_fd, hpos.data(), cnt * 8, n_sep * 8, "the index file");
+                        n_sep += cnt;
+                    };
+                    if (found <= pos_cap) {
+                        flush_pos(found);
+                    } else {
+                        for (size_t lo = 0; lo < kk; lo += pos_cap) {
+                            found = ids_find(ids + lo, std::min(pos_cap, kk - lo), (int)sizeof(OutT), O.separator_id,
+                                             k_done + lo, D.pos.p, pos_cap, s, D.stat);
+                            flush_pos(found);
+                        }
+                    }
+                }
+                st.stats_ms += since(t3);
+                {
+                    std::lock_guard<std::mutex> g(qm);
+                    guard.armed = false;
+                    jobs.push_back(Job{id_slot, kk, k_done});
+                }
+                qcv.notify_all();
+                k_done += kk;
+                id_slot ^= 1;
+                // the carry to the front
+                const size_t rest = total - e_end;
+                if (rest) {
+                    if (rest <= e_end) {
+                        BPE_HIP(hipMemcpyAsync(D.text.p, D.text.p + e_end, rest, hipMemcpyDeviceToDevice, s));
+                    } else {
+                        D.move.reserve(rest);
+                        BPE_HIP(hipMemcpyAsync(D.move.p, D.text.p + e_end, rest, hipMemcpyDeviceToDevice, s));
+                        BPE_HIP(hipMemcpyAsync(D.text.p, D.move.p, rest, hipMemcpyDeviceToDevice, s));
+                    }
+                    BPE_HIP(hipStreamSynchronize(s));
+                }
+                carry = rest;
+            } else {
+                carry = total;
+            }
+            if (w.eof) {
+                carry = 0;
+                chars = 0;
+                hold_prev = 0;
+                if (file_off) file_off[w.file + 1] = k_done;
+            }
+        }
+        if (counts) to_host(counts, D.counts.p, n_counts * 8, s);
+    } catch (...) {
+        join_all();
+        throw;
+    }
+    {   // every queued write done
+        std::lock_guard<std::mutex> g(qm);
+        jobs_closed = true;
+    }
+    qcv.notify_all();
+    writer.join();
+    reader.join();
+    if (write_err) std::rethrow_exception(write_err);
+    st.n_ids = k_done;
+    st.n_separators = n_sep;
+    st.read_ms = read_ms;
+    st.write_ms = write_ms;
+    st.device_bytes = D.raw[0].bytes() + D.raw[1].bytes() + D.text.bytes() + D.move.bytes() + D.ids[0].bytes() +
+                      D.ids[1].bytes() + D.pos.bytes() + (counts ? D.counts.bytes() : 0);
+}
+
 }  // namespace
 }  // namespace bpe
 
@@ -2651,6 +3016,71 @@ int bpe_tok_encode_file_u16(bpe_tokenizer* tok, const char* path, size_t chars_p
         *n_out = k;
         if (phase_ms) std::memcpy(phase_ms, ph, sizeof(ph));
     });
+}
+
+int bpe_tok_encode_files(bpe_tokenizer* tok, const char* const* paths, size_t n_paths, const char* out_path,
+                         const bpe_dataset_opts* opts, uint64_t* file_id_offsets, uint64_t* id_counts,
+                         size_t n_counts, bpe_dataset_stats* stats) {
+    // the outputs under temporary names beside their paths: renamed after success, removed after an error
+    struct TmpFile {
+        std::string path, tmp;
+        int fd = -1;
+        void open(const char* p) {
+            path = p;
+            tmp = path + ".tmp" + std::to_string((long long)::getpid());
+            fd = ::open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+            if (fd < 0) throw bpe::Error{BPE_E_IO, "cannot create " + tmp, errno};
+        }
+        void commit() {
+            const int rc = ::close(fd);
+            fd = -1;
+            if (rc != 0 || ::rename(tmp.c_str(), path.c_str()) != 0)
+                throw bpe::Error{BPE_E_IO, "cannot write " + path, errno};
+            tmp.clear();
+        }
+        ~TmpFile() {
+            if (fd >= 0) ::close(fd);
+            if (!tmp.empty()) ::unlink(tmp.c_str());
+        }
+    };
+    try {
+        BPE_REQUIRE(tok && out_path && opts && (n_paths == 0 || paths), BPE_E_ARG, "NULL argument");
+        const bpe_dataset_opts& O = *opts;
+        BPE_REQUIRE(O.chars_per_piece > 0, BPE_E_ARG, "chars_per_piece must be positive");
+        BPE_REQUIRE(O.window_bytes == 0 || O.window_bytes >= 65536, BPE_E_ARG, "window_bytes must be at least 65536");
+        BPE_REQUIRE(O.id_bytes == 2 || O.id_bytes == 4, BPE_E_ARG, "id_bytes must be 2 or 4");
+        BPE_REQUIRE((O.has_separator != 0) == (O.index_path != nullptr), BPE_E_ARG,
+                    "a separator needs an index path, and an index path a separator");
+        BPE_REQUIRE(!id_counts || (n_counts > 0 && n_counts <= (1ull << 32)), BPE_E_ARG, "bad id table size");
+        for (size_t i = 0; i < n_paths; ++i) BPE_REQUIRE(paths[i], BPE_E_ARG, "NULL path");
+        bpe_dataset_stats st{};
+        if (file_id_offsets) std::fill(file_id_offsets, file_id_offsets + n_paths + 1, (uint64_t)0);
+        if (id_counts) std::fill(id_counts, id_counts + n_counts, (uint64_t)0);
+        TmpFile out, idx;
+        out.open(out_path);
+        if (O.index_path) idx.open(O.index_path);
+        if (n_paths) {
+            int dev = 0;
+            BPE_HIP(hipGetDevice(&dev));
+            if (O.id_bytes == 2)
+                bpe::encode_files_pipelined<uint16_t>(*tok, paths, n_paths, out.fd, idx.fd, O, file_id_offsets,
+                                                      id_counts, n_counts, st, dev);
+            else
+                bpe::encode_files_pipelined<uint32_t>(*tok, paths, n_paths, out.fd, idx.fd, O, file_id_offsets,
+                                                      id_counts, n_counts, st, dev);
+        }
+        if (O.index_path) idx.commit();
+        out.commit();
+        if (stats) *stats = st;
+        bpe::set_error(0, "");
+        return BPE_OK;
+    } catch (const bpe::Error& e) {
+        bpe::set_error(e.code, e.msg, e.sys_errno);
+        return e.code;
+    } catch (const std::bad_alloc&) {
+        bpe::set_error(BPE_E_NOMEM, "host allocation failed");
+        return BPE_E_NOMEM;
+    }
 }
 
 int bpe_tok_encode_chunks(bpe_tokenizer* tok, const uint8_t* utf8, size_t n, const uint64_t* starts,

@@ -57,6 +57,22 @@ struct PieceScratch {
 uint64_t piece_starts_range(const uint8_t* d_text, size_t n, size_t k, uint64_t c_base, uint64_t offset,
                             hipStream_t stream, std::vector<uint64_t>& out, PieceScratch* scratch = nullptr);
 
+// ---------------------------------------------------------------- id stream statistics (idstats.hip)
+// Ids of elem_bytes 2, 4 or 8 in device memory, aligned to their own size only.  Both calls return
+// once their result is complete; scratch keeps the device arrays across calls.
+struct IdScratch {
+    DevBuf<unsigned long long> blk_cnt, blk_off, flags;
+    DevBuf<uint8_t> tmp;
+};
+// d_counts[id] += occurrences (64-bit).  An id at or above n_counts: Error{BPE_E_ARG} naming the
+// smallest one, and the table is then not to be used.
+void ids_histogram(const void* d_ids, size_t n, int elem_bytes, unsigned long long* d_counts, size_t n_counts,
+                   hipStream_t stream, IdScratch& scratch);
+// base + i for every i with ids[i] == value, ascending, the first `cap` of them into d_pos; returns
+// how many there are (more than cap: call again with room for all)
+size_t ids_find(const void* d_ids, size_t n, int elem_bytes, uint64_t value, uint64_t base, unsigned long long* d_pos,
+                size_t cap, hipStream_t stream, IdScratch& scratch);
+
 // ---------------------------------------------------------------- unique-word count
 struct WordCounts {
     DevBuf<unsigned long long> kv;    // cap x {key, count} (layout: text.hip), key 0 = empty
