@@ -385,6 +385,69 @@ int bpe_ids_histogram_device(const void* d_ids, size_t n, int elem_bytes, uint64
  * again with room for all).  d_ids as above.  Returns once the positions are written. */
 int bpe_ids_find_device(const void* d_ids, size_t n, int elem_bytes, uint64_t value, uint64_t base,
                         uint64_t* d_pos_out, size_t cap, size_t* n_out, void* hip_stream);
+/* The batch loader (the reference's load_batch, models/util.py:37-57): windows of an id stream ->
+ * the dense matrices of a training step, in one launch.  For every row r < n_rows and t < row_len
+ *     inputs[r, t]  = ids[src[r] + t]
+ *     targets[r, t] = ids[src[r] + t + 1]          (d_targets NULL: not written)
+ * int32 (out_elem_bytes 4) or int64 (8), row-major [n_rows, row_len].  Each row's row_len + 1 ids are
+ * read once, as 16-byte vectors on the 16-byte grid, and both matrices are written from them with
+ * 16-byte stores wherever the output's alignment allows.  All pointers are device memory.
+ *
+ * d_ids: n ids of elem_bytes 2 or 4 (unsigned), aligned to elem_bytes only.  d_src: n_rows int64
+ * offsets into d_ids.  d_pos: NULL, or n_rows int64: the rows' positions in the whole stream when
+ * d_ids is not that stream (the staged path below gathers the rows first); NULL: pos = src.
+ *
+ * Document-aware outputs, from the sorted separator positions d_sep_pos[n_sep] (what encode_files
+ * writes to index_path; a separator ends a document and belongs to it), with g = pos[r] + t:
+ *     positions[r, t] = g - (the largest separator position < g, or -1) - 1       int64
+ *     doc_ids[r, t]   = the number of separator positions in [pos[r], g)           int32
+ * Either may be NULL.  Both are computed from the index alone (n_sep == 0 is valid: the position is
+ * then g itself), not from the ids.
+ * flags & BPE_BATCH_IGNORE: targets[r, t] = ignore_index where inputs[r, t] == separator_id.
+ *
+ * Checks, on the device.  No load falls outside d_ids[0, n): a row with src[r] < 0 or src[r] > n -
+ * row_len - 1 (n - row_len without targets) is neither read nor written.  With out_elem_bytes 4 an id
+ * of 2^31 or more that is written is reported (the matrices are then not to be used); ids outside
+ * every row are not looked at.  Both reports go through the 8-byte word d_status (NULL: nothing is
+ * reported), which the call sets to ~0 first.  flags & BPE_BATCH_CHECK (d_status required): the
+ * word is copied back, the stream is synchronised, and the call returns BPE_E_ARG with "row <r>
+ * starts outside [0, <last valid>]" for the smallest such row, else BPE_E_LIMIT with the smallest
+ * such id in the message, as bpe_ids_pack_rows_device.  Without the bit the call only enqueues on
+ * hip_stream and returns; the word then holds ~0, the smallest bad row, or 2^62 | the smallest id.
+ * row_len >= 1; n_rows == 0 is valid.  Runs on the current device. */
+#define BPE_BATCH_CHECK 1
+#define BPE_BATCH_IGNORE 2
+typedef struct bpe_batch_args {
+    size_t n_rows, row_len;
+    int out_elem_bytes;          /* 4 or 8: inputs and targets */
+    int flags;
+    void* d_inputs;
+    void* d_targets;             /* NULL: none */
+    int64_t* d_positions;        /* NULL: none */
+    int32_t* d_doc_ids;          /* NULL: none */
+    const uint64_t* d_sep_pos;
+    size_t n_sep;
+    uint64_t separator_id;       /* BPE_BATCH_IGNORE */
+    int64_t ignore_index;
+    uint64_t* d_status;
+} bpe_batch_args;
+int bpe_ids_batch_rows_device(const void* d_ids, size_t n, int elem_bytes, const int64_t* d_src,
+                              const int64_t* d_pos, const bpe_batch_args* args, void* hip_stream);
+/* The same for a stream in host memory (an array, an np.memmap of a file that is not to be held in
+ * HBM): ids[0, n) and starts[n_rows] are host memory, the outputs in args device memory.  At most 8
+ * host threads (one per 512 KiB of rows) copy the rows' row_len + 1 ids each into a pinned buffer
+ * behind the rows' offsets, one hipMemcpyAsync moves that buffer to a device buffer of the handle,
+ * and the kernel above runs on it with pos = starts.  starts are checked on the host (BPE_E_ARG,
+ * the message as above) before anything is enqueued.  The handle owns two pinned and two device
+ * buffers with an event each and alternates between them: a call waits only for the copy and the
+ * kernel of the call before the previous one, so two calls in a row are issued without a
+ * synchronisation.  Buffers grow as needed and stay until bpe_batch_stage_free.  A handle belongs
+ * to the device current at its creation; one caller at a time. */
+typedef struct bpe_batch_stage bpe_batch_stage;
+int bpe_batch_stage_create(bpe_batch_stage** out);
+int bpe_batch_stage_rows(bpe_batch_stage* stage, const void* ids, size_t n, int elem_bytes, const int64_t* starts,
+                         const bpe_batch_args* args, void* hip_stream);
+void bpe_batch_stage_free(bpe_batch_stage* stage);
 /* encode(text) on n_gpus devices of this process (<= 0: every visible one; SURVEY.md 8b's n_gpus):
  * the text is cut at safe split points that no special token spans, each device encodes its
  * piece, the ids are concatenated -- identical to bpe_tok_encode (tokenizer.py:111-138). */

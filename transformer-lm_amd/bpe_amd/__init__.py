@@ -18,4 +18,8 @@ def __getattr__(name):
     if name in ("encode_files", "id_counts", "id_positions"):
         from . import encode
         return getattr(encode, name)
+    # the batch loader (bpe_amd.batches) likewise: it needs NumPy, which the tokenizer path does not
+    if name in ("load_batch", "TokenStore"):
+        from . import batches
+        return getattr(batches, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

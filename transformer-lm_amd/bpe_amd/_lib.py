@@ -78,6 +78,19 @@ class DatasetStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+BATCH_CHECK, BATCH_IGNORE = 1, 2
+
+
+class BatchArgs(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_size_t), ("row_len", ctypes.c_size_t),
+                ("out_elem_bytes", ctypes.c_int), ("flags", ctypes.c_int),
+                ("d_inputs", ctypes.c_void_p), ("d_targets", ctypes.c_void_p),
+                ("d_positions", ctypes.c_void_p), ("d_doc_ids", ctypes.c_void_p),
+                ("d_sep_pos", ctypes.c_void_p), ("n_sep", ctypes.c_size_t),
+                ("separator_id", ctypes.c_uint64), ("ignore_index", ctypes.c_int64),
+                ("d_status", ctypes.c_void_p)]
+
+
 HOST_ALLREDUCE_FN =ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p,
                                      ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t)
 
@@ -160,6 +173,10 @@ _SIGS = [
     ("bpe_ids_histogram_device", ctypes.c_int, [_P, _SZ, ctypes.c_int, _P, _SZ, _P]),
     ("bpe_ids_find_device", ctypes.c_int, [_P, _SZ, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, _P, _SZ,
                                            ctypes.POINTER(_SZ), _P]),
+    ("bpe_ids_batch_rows_device", ctypes.c_int, [_P, _SZ, ctypes.c_int, _P, _P, ctypes.POINTER(BatchArgs), _P]),
+    ("bpe_batch_stage_create", ctypes.c_int, [ctypes.POINTER(_P)]),
+    ("bpe_batch_stage_rows", ctypes.c_int, [_P, _P, _SZ, ctypes.c_int, _P, ctypes.POINTER(BatchArgs), _P]),
+    ("bpe_batch_stage_free", None, [_P]),
     ("bpe_tok_release_buffers", ctypes.c_int, [_P]),
     ("bpe_tok_free", None, [_P]),
     ("bpe_dec_create", ctypes.c_int, [_U8P, _SZ, ctypes.POINTER(_P)]),
