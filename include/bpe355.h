@@ -530,6 +530,51 @@ int bpe_utf8_chunk_starts_device(const uint8_t* d_text, size_t n, size_t chars_p
  * does not fit (the reference would silently wrap it). */
 int bpe_ids_to_u16_device(const uint32_t* d_ids, size_t n, uint16_t* d_out, void* hip_stream);
 
+/* ---------------------------------------------------------------- ill-formed UTF-8 */
+/* Every entry point above that reads text decodes it strictly (BPE_E_UTF8).  The calls below add
+ * CPython's errors="replace" (mode 1) and errors="ignore" (mode 2): each maximal subpart of an
+ * ill-formed subsequence becomes one U+FFFD (EF BF BD) or is dropped, exactly
+ * bytes.decode("utf-8", errors).  Mode 0 is strict and runs exactly the code of the call it
+ * extends.  A clean input pays nothing: the repair runs only after the strict validation failed. */
+#define BPE_UTF8_STRICT 0
+#define BPE_UTF8_REPLACE 1
+#define BPE_UTF8_IGNORE 2
+typedef struct bpe_utf8_stats {
+    uint64_t n_units;   /* spans replaced or dropped */
+    uint64_t n_bytes;   /* the input bytes they covered */
+    uint64_t first;     /* where the first span starts (what strict mode reports), ~0: none */
+} bpe_utf8_stats;
+/* d_out[0, *n_out) = bytes(d_in[0, n)).decode("utf-8", errors).encode("utf-8") for mode 1 or 2,
+ * all in device memory on the current device; d_in is not modified and must not overlap d_out.
+ * d_out == NULL: size query (*n_out and *stats are set, nothing is written).  cap < *n_out:
+ * BPE_E_ARG with *n_out set.  Replace grows a text up to 3x; the offsets are 64-bit.  stats may be
+ * NULL.  Returns once d_out is written. */
+int bpe_utf8_repair_device(const uint8_t* d_in, size_t n, int mode, uint8_t* d_out, size_t cap, size_t* n_out,
+                           bpe_utf8_stats* stats, void* hip_stream);
+/* the repair kernel's vector width (bytes a thread classifies) and tile (bytes a workgroup
+ * repairs per step): where its code paths meet, for tests */
+int bpe_utf8_repair_geometry(size_t* unit_bytes, size_t* tile_bytes);
+/* bpe_text_prepare_device with an errors mode: the repair, then universal newlines.  d_out ==
+ * NULL: *n_out = the bytes d_out must hold (the repaired length; the translated text is no
+ * longer).  d_out may be d_in when it holds that many bytes. */
+int bpe_text_prepare_device_ex(const uint8_t* d_in, size_t n, int mode, uint8_t* d_out, size_t cap, size_t* n_out,
+                               bpe_utf8_stats* stats, void* hip_stream);
+/* The errors mode of a counter's later bpe_counter_add_file / _add_buffer / _add_device calls
+ * (0 at creation).  In mode 1 or 2 a window whose validation fails is repaired where it lies in
+ * HBM and counted again; windows end at ASCII bytes, so the result is the whole file's. */
+int bpe_counter_set_errors(bpe_counter* c, int mode);
+/* what the last such call repaired; first is a position in that input */
+int bpe_counter_utf8_report(const bpe_counter* c, bpe_utf8_stats* out);
+/* The errors mode of a tokenizer's later bpe_tok_encode_files calls (0 at creation): a raw range
+ * that fails validation is repaired before the newline translation; pieces count characters of
+ * the repaired text (U+FFFD is one). */
+int bpe_tok_set_errors(bpe_tokenizer* tok, int mode);
+/* what the last bpe_tok_encode_files call repaired: the totals (first: a position in the raw
+ * file *first_file, an index into paths), and per file the spans (file_units: NULL or n_files
+ * entries; files beyond the last call's count get 0) */
+int bpe_tok_utf8_report(const bpe_tokenizer* tok, bpe_utf8_stats* total, uint64_t* first_file,
+                        uint64_t* file_units, size_t n_files);
+
 /* ---------------------------------------------------------------- helpers */
 /* Largest p <= pos such that splitting the text at p does not change its pre-tokenization
  * (a U+0020 between two ASCII non-space bytes), or 0. Used to shard a corpus into slabs. */

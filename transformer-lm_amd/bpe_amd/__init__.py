@@ -8,6 +8,7 @@ libbpe355.so (HIP, gfx950); there is no CPU fallback.
 from .train import (train_bpe, train_bpe_bytes, train_bpe_device, last_train_stats,  # noqa: F401
                     set_num_gpus, num_gpus, release_device_memory)
 from .counter import WordCounter, train_bpe_files, train_bpe_word_counts  # noqa: F401
+from .utf8 import repair_utf8, last_utf8_errors  # noqa: F401
 from .vocab import Vocab  # noqa: F401
 from .tokenizer import Tokenizer  # noqa: F401
 

@@ -78,6 +78,10 @@ class DatasetStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class Utf8Stats(ctypes.Structure):
+    _fields_ = [("n_units", ctypes.c_uint64), ("n_bytes", ctypes.c_uint64), ("first", ctypes.c_uint64)]
+
+
 BATCH_CHECK, BATCH_IGNORE = 1, 2
 
 
@@ -192,6 +196,15 @@ _SIGS = [
     ("bpe_text_prepare_device", ctypes.c_int, [_P, _SZ, _P, ctypes.POINTER(_SZ), _P]),
     ("bpe_utf8_chunk_starts_device", ctypes.c_int, [_P, _SZ, _SZ, _P, _SZ, ctypes.POINTER(_SZ), _P]),
     ("bpe_ids_to_u16_device", ctypes.c_int, [_P, _SZ, _P, _P]),
+    ("bpe_utf8_repair_device", ctypes.c_int, [_P, _SZ, ctypes.c_int, _P, _SZ, ctypes.POINTER(_SZ),
+                                              ctypes.POINTER(Utf8Stats), _P]),
+    ("bpe_utf8_repair_geometry", ctypes.c_int, [ctypes.POINTER(_SZ), ctypes.POINTER(_SZ)]),
+    ("bpe_text_prepare_device_ex", ctypes.c_int, [_P, _SZ, ctypes.c_int, _P, _SZ, ctypes.POINTER(_SZ),
+                                                  ctypes.POINTER(Utf8Stats), _P]),
+    ("bpe_counter_set_errors", ctypes.c_int, [_P, ctypes.c_int]),
+    ("bpe_counter_utf8_report", ctypes.c_int, [_P, ctypes.POINTER(Utf8Stats)]),
+    ("bpe_tok_set_errors", ctypes.c_int, [_P, ctypes.c_int]),
+    ("bpe_tok_utf8_report", ctypes.c_int, [_P, ctypes.POINTER(Utf8Stats), ctypes.POINTER(ctypes.c_uint64), _P, _SZ]),
     ("bpe_safe_split", _SZ, [_U8P, _SZ, _SZ]),
     ("bpe_synth_corpus_device", ctypes.c_int, [_P, _SZ, ctypes.c_uint64, ctypes.c_int,
                                                ctypes.c_uint64, _P]),

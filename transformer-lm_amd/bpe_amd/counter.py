@@ -15,6 +15,7 @@ from typing import Iterable, List, Mapping
 
 from . import _lib
 from . import train as _train
+from . import utf8 as _utf8
 
 __all__ = ["WordCounter", "train_bpe_files", "train_bpe_word_counts"]
 
@@ -42,33 +43,57 @@ class WordCounter:
             raise ValueError("the WordCounter is closed")
         return self._h
 
-    def add_file(self, path: str | os.PathLike, window_bytes: int | None = None):
-        """The file as train_bpe reads it, counted in windows of about window_bytes (None: the
-        library's default, 8 GiB) so that only one window is in device memory at a time.  After
-        an error (FileNotFoundError / OSError, UnicodeDecodeError) the counter is unchanged."""
-        rc = _lib.lib().bpe_counter_add_file(self._handle(), os.fsencode(os.fspath(path)), int(window_bytes or 0))
-        _check(rc, f"WordCounter.add_file({os.fspath(path)!r})")
+    def _decode_as(self, errors: str, call, what: str, path=None):
+        """Run one add call under the errors mode; a non-strict call leaves its report in
+        bpe_amd.last_utf8_errors().  "strict" runs the call exactly as it always did."""
+        mode = _utf8.mode_of(errors)
+        if mode == 0:
+            _check(call(), what)
+            return self
+        L = _lib.lib()
+        h = self._handle()
+        _check(L.bpe_counter_set_errors(h, mode), what)
+        try:
+            _check(call(), what)
+            st = _lib.Utf8Stats()
+            _check(L.bpe_counter_utf8_report(h, ctypes.byref(st)), what)
+        finally:
+            L.bpe_counter_set_errors(h, 0)
+        d = _utf8.stats_dict(st)
+        _utf8.note(errors, d["n_units"], d["n_bytes"], (path, d["first"]) if d["first"] is not None else None)
         return self
 
-    def add_bytes(self, data: bytes):
+    def add_file(self, path: str | os.PathLike, window_bytes: int | None = None, errors: str = "strict"):
+        """The file as train_bpe reads it, counted in windows of about window_bytes (None: the
+        library's default, 8 GiB) so that only one window is in device memory at a time.  After
+        an error (FileNotFoundError / OSError, UnicodeDecodeError) the counter is unchanged.
+        errors: "strict", or "replace" / "ignore" as open(path, encoding="utf-8", errors=...)
+        reads the file: a window with ill-formed UTF-8 is repaired on the device and counted."""
+        _utf8.mode_of(errors)
+        return self._decode_as(errors, lambda: _lib.lib().bpe_counter_add_file(
+            self._handle(), os.fsencode(os.fspath(path)), int(window_bytes or 0)),
+            f"WordCounter.add_file({os.fspath(path)!r})", os.fspath(path))
+
+    def add_bytes(self, data: bytes, errors: str = "strict"):
         """Raw file bytes (decoded exactly like the file would be): one document."""
+        _utf8.mode_of(errors)
         data = bytes(data)
-        _check(_lib.lib().bpe_counter_add_buffer(self._handle(), data, len(data)), "WordCounter.add_bytes")
-        return self
+        return self._decode_as(errors, lambda: _lib.lib().bpe_counter_add_buffer(self._handle(), data, len(data)),
+                               "WordCounter.add_bytes")
 
     def add_text(self, text: str):
         return self.add_bytes(text.encode("utf-8"))
 
-    def add_tensor(self, t):
+    def add_tensor(self, t, errors: str = "strict"):
         """A contiguous uint8 tensor on the counter's GPU holding raw file bytes; it is not modified."""
+        _utf8.mode_of(errors)
         import torch
         if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
             raise ValueError("add_tensor needs a contiguous uint8 cuda tensor")
         stream = torch.cuda.current_stream(t.device).cuda_stream
-        rc = _lib.lib().bpe_counter_add_device(self._handle(), ctypes.c_void_p(t.data_ptr()), t.numel(),
-                                               ctypes.c_void_p(stream or None))
-        _check(rc, "WordCounter.add_tensor")
-        return self
+        return self._decode_as(errors, lambda: _lib.lib().bpe_counter_add_device(
+            self._handle(), ctypes.c_void_p(t.data_ptr()), t.numel(), ctypes.c_void_p(stream or None)),
+            "WordCounter.add_tensor")
 
     def add_counts(self, counts: Mapping):
         """Pre-counted words {str | bytes: int}; words under 2 bytes carry no pair and are dropped."""
@@ -155,12 +180,26 @@ def _train_and_release(counter, fill, vocab_size, special_tokens):
             pass
 
 
-def train_bpe_files(paths, vocab_size: int, special_tokens: List[str] = [], window_bytes: int | None = None):
+def train_bpe_files(paths, vocab_size: int, special_tokens: List[str] = [], window_bytes: int | None = None,
+                    errors: str = "strict"):
     """train_bpe over several files, each one document, none of them held in device memory beyond
-    one window of window_bytes: what the reference gives on a corpus whose documents they are."""
-    def fill(c):
-        for p in paths:
-            c.add_file(p, window_bytes)
+    one window of window_bytes: what the reference gives on a corpus whose documents they are.
+    errors: as WordCounter.add_file; last_utf8_errors() then sums over the files."""
+    if _utf8.mode_of(errors) == 0:
+        def fill(c):
+            for p in paths:
+                c.add_file(p, window_bytes)
+    else:
+        def fill(c):
+            n_units = n_bytes = 0
+            first = None
+            for p in paths:
+                c.add_file(p, window_bytes, errors=errors)
+                r = _utf8.last_utf8_errors()
+                n_units += r["n_units"]
+                n_bytes += r["n_bytes"]
+                first = first or r["first"]
+            _utf8.note(errors, n_units, n_bytes, first)
     return _train_and_release(WordCounter(), fill, vocab_size, special_tokens)
 
 

@@ -29,6 +29,7 @@ import stat
 import numpy as np
 
 from . import _lib
+from . import utf8 as _utf8
 from .tokenizer import Tokenizer
 
 fname = {   # encode.py:8-15
@@ -43,18 +44,47 @@ fname = {   # encode.py:8-15
 CHARS_PER_PIECE = 1024 * 1024   # encode.py:33 f.read(1024 * 1024)
 
 
-def encode_device_u16(tokenizer: Tokenizer, raw, chars_per_piece: int = CHARS_PER_PIECE) -> np.ndarray:
-    """The reference's encode.py ids for the raw file bytes held in the device tensor `raw`
-    (uint8; overwritten by the text-mode read), as np.uint16 in host memory."""
+def _prepare_repaired(raw, mode: int, errors: str, path):
+    """The non-strict text-mode read of a tensor whose strict read failed: a new tensor holding
+    the repaired, newline-translated text, and its length.  raw is not modified."""
     import torch
     L = _lib.lib()
     n = raw.numel()
+    need, st = ctypes.c_size_t(0), _lib.Utf8Stats()
+    _lib.check(L.bpe_text_prepare_device_ex(ctypes.c_void_p(raw.data_ptr()), n, mode, None, 0, ctypes.byref(need),
+                                            ctypes.byref(st), None), "read")
+    out = torch.empty(max(need.value, 1), dtype=torch.uint8, device=raw.device)
+    m = ctypes.c_size_t(0)
+    _lib.check(L.bpe_text_prepare_device_ex(ctypes.c_void_p(raw.data_ptr()), n, mode, ctypes.c_void_p(out.data_ptr()),
+                                            need.value, ctypes.byref(m), ctypes.byref(st), None), "read")
+    d = _utf8.stats_dict(st)
+    _utf8.note(errors, d["n_units"], d["n_bytes"], (path, d["first"]) if d["first"] is not None else None)
+    return out, m.value
+
+
+def encode_device_u16(tokenizer: Tokenizer, raw, chars_per_piece: int = CHARS_PER_PIECE, errors: str = "strict",
+                      _path=None) -> np.ndarray:
+    """The reference's encode.py ids for the raw file bytes held in the device tensor `raw`
+    (uint8; overwritten by the text-mode read), as np.uint16 in host memory.  errors "replace" or
+    "ignore": bytes the strict read refuses are repaired first, as open(..., errors=...) reads them."""
+    mode = _utf8.mode_of(errors)
+    import torch
+    L = _lib.lib()
+    n = raw.numel()
+    if mode:
+        _utf8.note(errors, 0, 0, None)
     if n == 0:
         return np.zeros(0, dtype=np.uint16)
     m = ctypes.c_size_t(0)
-    _lib.check(L.bpe_text_prepare_device(ctypes.c_void_p(raw.data_ptr()), n, ctypes.c_void_p(raw.data_ptr()),
-                                         ctypes.byref(m), None), "read")
-    m = m.value
+    rc = L.bpe_text_prepare_device(ctypes.c_void_p(raw.data_ptr()), n, ctypes.c_void_p(raw.data_ptr()),
+                                   ctypes.byref(m), None)
+    if mode and rc == _lib.BPE_E_UTF8:   # validation failed before anything was written: repair, then read
+        raw, m = _prepare_repaired(raw, mode, errors, _path)
+        if m == 0:
+            return np.zeros(0, dtype=np.uint16)
+    else:
+        _lib.check(rc, "read")
+        m = m.value
     ns = ctypes.c_size_t(0)
     _lib.check(L.bpe_utf8_chunk_starts_device(ctypes.c_void_p(raw.data_ptr()), m, chars_per_piece, None, 0,
                                               ctypes.byref(ns), None), "chunk starts")
@@ -77,14 +107,18 @@ def encode_device_u16(tokenizer: Tokenizer, raw, chars_per_piece: int = CHARS_PE
     return host
 
 
-def encode_bytes_u16(tokenizer: Tokenizer, data: bytes, chars_per_piece: int = CHARS_PER_PIECE) -> np.ndarray:
+def encode_bytes_u16(tokenizer: Tokenizer, data: bytes, chars_per_piece: int = CHARS_PER_PIECE,
+                     errors: str = "strict", _path=None) -> np.ndarray:
     """The reference's encode.py ids for a file whose raw bytes are `data`, as np.uint16."""
+    mode = _utf8.mode_of(errors)
     import torch
     if len(data) == 0:
+        if mode:
+            _utf8.note(errors, 0, 0, None)
         return np.zeros(0, dtype=np.uint16)
     raw = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda")
     torch.cuda.synchronize()
-    return encode_device_u16(tokenizer, raw, chars_per_piece)
+    return encode_device_u16(tokenizer, raw, chars_per_piece, errors, _path)
 
 
 def read_file_device(path):
@@ -124,12 +158,22 @@ def encode_file_native(tokenizer: Tokenizer, path, chars_per_piece: int = CHARS_
 
 
 def encode_file(tokenizer: Tokenizer, input_path, output_path=None, fmt: str = "pt",
-                chars_per_piece: int = CHARS_PER_PIECE, keep_device_buffers: bool = False) -> np.ndarray:
+                chars_per_piece: int = CHARS_PER_PIECE, keep_device_buffers: bool = False,
+                errors: str = "strict") -> np.ndarray:
     """Encode a text file like encode.py:main; write it if output_path is given.  The device
     buffers of the bulk encoder (about 3 bytes of HBM per file byte) are released afterwards
     unless keep_device_buffers (several files in a row: re-allocating tens of GB costs the driver
-    up to seconds per call)."""
-    if stat.S_ISREG(os.stat(input_path).st_mode):   # missing: FileNotFoundError, as open() raises
+    up to seconds per call).  errors "replace" or "ignore": the file is read as open(path,
+    encoding="utf-8", errors=...) reads it; it then goes to the device whole and through the
+    text-prepare step with that mode (encode_device_u16), not through the overlapped reader."""
+    if _utf8.mode_of(errors):
+        raw = read_file_device(input_path)
+        if raw is None:
+            with open(input_path, "rb") as f:
+                pt = encode_bytes_u16(tokenizer, f.read(), chars_per_piece, errors, os.fspath(input_path))
+        else:
+            pt = encode_device_u16(tokenizer, raw, chars_per_piece, errors, os.fspath(input_path))
+    elif stat.S_ISREG(os.stat(input_path).st_mode):   # missing: FileNotFoundError, as open() raises
         try:
             pt = encode_file_native(tokenizer, input_path, chars_per_piece)
         finally:
@@ -172,7 +216,7 @@ def _same_file(a, b) -> bool:
 
 def encode_files(tokenizer: Tokenizer, paths, output_path, *, dtype=None, window_bytes=None,
                  chars_per_piece: int = CHARS_PER_PIECE, separator=None, index_path=None,
-                 count_ids: bool = False, keep_device_buffers: bool = False) -> dict:
+                 count_ids: bool = False, keep_device_buffers: bool = False, errors: str = "strict") -> dict:
     """Encode many text files of any size into one token file.
 
     Each file is encoded exactly as encode_file encodes it alone (text-mode read, pieces of
@@ -196,9 +240,15 @@ def encode_files(tokenizer: Tokenizer, paths, output_path, *, dtype=None, window
     are as they were before the call.  Runs on the current device (set_num_gpus does not apply).
     The device buffers are released afterwards unless keep_device_buffers.
 
+    errors "replace" or "ignore": a raw range with ill-formed UTF-8 is repaired on the device as
+    open(path, encoding="utf-8", errors=...) decodes it (pieces count characters of the repaired
+    text, U+FFFD is one); the result then also carries n_replaced (spans replaced or dropped) and
+    file_replaced (np.int64, one entry per path), and last_utf8_errors() reports the call.
+
     Returns a dict: n_ids, dtype, file_offsets (np.int64, len(paths) + 1), n_bytes, n_pieces,
     n_windows, max_window_bytes, n_separators, n_grows, device_bytes, the busy milliseconds
     read_ms, decode_ms, encode_ms, write_ms and stats_ms, and id_counts when asked for."""
+    mode = _utf8.mode_of(errors)
     paths = [os.fspath(p) for p in paths]
     if dtype is not None:
         try:
@@ -244,16 +294,30 @@ def encode_files(tokenizer: Tokenizer, paths, output_path, *, dtype=None, window
     offsets = np.zeros(len(paths) + 1, dtype=np.uint64)
     counts = np.zeros(top + 1, dtype=np.uint64) if count_ids else None
     st = _lib.DatasetStats()
+    fix, fix_file, fix_units = _lib.Utf8Stats(), ctypes.c_uint64(0), np.zeros(max(1, len(paths)), dtype=np.uint64)
     try:
+        if mode:
+            _lib.check(L.bpe_tok_set_errors(tokenizer._device(), mode), "encode files")
         rc = L.bpe_tok_encode_files(tokenizer._device(), arr, len(paths), os.fsencode(os.fspath(output_path)),
                                     ctypes.byref(opts), offsets.ctypes.data,
                                     counts.ctypes.data if count_ids else None, counts.size if count_ids else 0,
                                     ctypes.byref(st))
         _lib.check(rc, "encode files")
+        if mode:
+            _lib.check(L.bpe_tok_utf8_report(tokenizer._device(), ctypes.byref(fix), ctypes.byref(fix_file),
+                                             fix_units.ctypes.data, len(paths)), "encode files")
     finally:
+        if mode:
+            L.bpe_tok_set_errors(tokenizer._device(), 0)
         if not keep_device_buffers:
             tokenizer.release_device_buffers()
     out = st.as_dict()
+    if mode:
+        d = _utf8.stats_dict(fix)
+        _utf8.note(errors, d["n_units"], d["n_bytes"],
+                   (paths[fix_file.value], d["first"]) if d["first"] is not None else None)
+        out["n_replaced"] = d["n_units"]
+        out["file_replaced"] = fix_units[:len(paths)].astype(np.int64)
     out["dtype"] = dtype
     out["file_offsets"] = offsets.astype(np.int64)
     if count_ids:

@@ -12,6 +12,7 @@ import os
 from typing import List
 
 from . import _lib
+from . import utf8 as _utf8
 
 __all__ = ["train_bpe", "train_bpe_bytes", "train_bpe_device", "last_train_stats", "set_num_gpus",
            "num_gpus", "release_device_memory"]
@@ -68,8 +69,29 @@ def _finish(rc, res, what, keep_device_buffers=True):
     return vocab, merges
 
 
+def _train_counted(add, errors, comm, split_file, vocab_size, special_tokens, keep_device_buffers):
+    """A non-strict train call: one document through a WordCounter on the current device.  The
+    trainer sees its corpus only through the {pre-token: count} multiset, so the result is what
+    train_bpe gives on the text CPython decodes with that errors mode."""
+    if comm is not None or split_file:
+        raise ValueError(f"errors={errors!r} cannot be combined with comm or split_file: "
+                         "the repair runs on one device")
+    from .counter import WordCounter
+    c = WordCounter()
+    try:
+        add(c)
+        return c.train(vocab_size, special_tokens)
+    finally:
+        c.close()
+        if not keep_device_buffers:
+            try:
+                release_device_memory(-1)
+            except Exception:
+                pass
+
+
 def train_bpe(input_path: str | os.PathLike, vocab_size: int, special_tokens: List[str] = [],
-              comm=None, split_file: bool = False, keep_device_buffers: bool = False):
+              comm=None, split_file: bool = False, keep_device_buffers: bool = False, errors: str = "strict"):
     """Train a byte-level BPE on the file at input_path (reference train.py:142-231).
 
     Without comm: one process on num_gpus() devices (set_num_gpus / BPE355_GPUS).
@@ -77,7 +99,13 @@ def train_bpe(input_path: str | os.PathLike, vocab_size: int, special_tokens: Li
     with split_file=True the whole corpus, of which each rank reads its share.
     keep_device_buffers: keep the corpus buffer and the counter's scratch (~5 bytes of HBM per
     corpus byte) for the next call instead of freeing them on return (bench.py's repeated steps).
+    errors: "strict" (the reference: UnicodeDecodeError), or "replace" / "ignore" as open(path,
+    encoding="utf-8", errors=...) decodes; then the file is counted by a WordCounter on the
+    current device (set_num_gpus does not apply; comm and split_file raise ValueError).
     """
+    if _utf8.mode_of(errors):
+        return _train_counted(lambda c: c.add_file(input_path, errors=errors), errors, comm, split_file,
+                              vocab_size, special_tokens, keep_device_buffers)
     L = _lib.lib()
     arr, n, _keep = _lib.c_strings(special_tokens)
     res = ctypes.c_void_p()
@@ -91,8 +119,12 @@ def train_bpe(input_path: str | os.PathLike, vocab_size: int, special_tokens: Li
 
 
 def train_bpe_bytes(data: bytes, vocab_size: int, special_tokens: List[str] = [], comm=None,
-                    keep_device_buffers: bool = False):
-    """train_bpe on the raw bytes of a file (decoded exactly like the file would be)."""
+                    keep_device_buffers: bool = False, errors: str = "strict"):
+    """train_bpe on the raw bytes of a file (decoded exactly like the file would be; errors as in
+    train_bpe)."""
+    if _utf8.mode_of(errors):
+        return _train_counted(lambda c: c.add_bytes(data, errors=errors), errors, comm, False,
+                              vocab_size, special_tokens, keep_device_buffers)
     L = _lib.lib()
     arr, n, _keep = _lib.c_strings(special_tokens)
     res = ctypes.c_void_p()

@@ -113,6 +113,8 @@ struct bpe_comm {
 struct bpe_counter {
     mutable std::mutex m;   // one call at a time per counter
     bpe::WordAccumulator acc;
+    int errors = 0;                            // BPE_UTF8_*: how the add calls decode (bpe_counter_set_errors)
+    bpe_utf8_stats report{0, 0, ~0ULL};        // what the last add call repaired
 };
 
 namespace bpe {
@@ -358,7 +360,8 @@ int bpe_counter_add_file(bpe_counter* c, const char* path, size_t window_bytes) 
         BPE_REQUIRE(path, BPE_E_ARG, "path is NULL");
         const bpe::Source src = bpe::Source::open_path(path);
         std::lock_guard<std::mutex> g(c->m);
-        bpe::counter_add_source(c->acc, src, window_bytes);
+        c->report = bpe_utf8_stats{0, 0, ~0ULL};
+        bpe::counter_add_source(c->acc, src, window_bytes, c->errors, &c->report);
     });
 }
 
@@ -368,7 +371,8 @@ int bpe_counter_add_buffer(bpe_counter* c, const uint8_t* data, size_t n) {
         BPE_REQUIRE(!n || data, BPE_E_ARG, "data is NULL");
         const bpe::Source src = bpe::Source::memory(data, n);
         std::lock_guard<std::mutex> g(c->m);
-        bpe::counter_add_source(c->acc, src, 0);
+        c->report = bpe_utf8_stats{0, 0, ~0ULL};
+        bpe::counter_add_source(c->acc, src, 0, c->errors, &c->report);
     });
 }
 
@@ -377,7 +381,26 @@ int bpe_counter_add_device(bpe_counter* c, const uint8_t* d_data, size_t n, void
         BPE_REQUIRE(c, BPE_E_ARG, "counter is NULL");
         BPE_REQUIRE(!n || d_data, BPE_E_ARG, "data is NULL");
         std::lock_guard<std::mutex> g(c->m);
-        bpe::counter_add_device(c->acc, d_data, n, (hipStream_t)hip_stream);
+        c->report = bpe_utf8_stats{0, 0, ~0ULL};
+        bpe::counter_add_device(c->acc, d_data, n, (hipStream_t)hip_stream, c->errors, &c->report);
+    });
+}
+
+int bpe_counter_set_errors(bpe_counter* c, int mode) {
+    return bpe::guarded([&] {
+        BPE_REQUIRE(c, BPE_E_ARG, "counter is NULL");
+        BPE_REQUIRE(mode >= BPE_UTF8_STRICT && mode <= BPE_UTF8_IGNORE, BPE_E_ARG,
+                    "mode must be 0 (strict), 1 (replace) or 2 (ignore)");
+        std::lock_guard<std::mutex> g(c->m);
+        c->errors = mode;
+    });
+}
+
+int bpe_counter_utf8_report(const bpe_counter* c, bpe_utf8_stats* out) {
+    return bpe::guarded([&] {
+        BPE_REQUIRE(c && out, BPE_E_ARG, "counter or out is NULL");
+        std::lock_guard<std::mutex> g(c->m);
+        *out = c->report;
     });
 }
 

@@ -59,9 +59,14 @@ void train_source_comm(const Source& src, bool split, int vocab_size, const std:
 // The default is a choice, not a measured optimum: 8 GiB of text plus the counter's scratch
 // (about 4 bytes per byte) is about 40 GB of HBM.
 constexpr size_t kDefaultWindow = (size_t)8 << 30;
-void counter_add_source(WordAccumulator& acc, const Source& src, size_t window_bytes);
+// errors (BPE_UTF8_*): 0 is strict.  In mode 1 or 2 a window whose validation fails is repaired
+// where it lies in HBM (utf8fix.hip) and counted again; report (may be NULL) gets what was
+// repaired, its first position relative to the source.
+void counter_add_source(WordAccumulator& acc, const Source& src, size_t window_bytes, int errors = 0,
+                        bpe_utf8_stats* report = nullptr);
 // the same for raw bytes already in device memory (one window; d_data is not modified)
-void counter_add_device(WordAccumulator& acc, const uint8_t* d_data, size_t n, hipStream_t stream);
+void counter_add_device(WordAccumulator& acc, const uint8_t* d_data, size_t n, hipStream_t stream, int errors = 0,
+                        bpe_utf8_stats* report = nullptr);
 // bpe_release_device_memory: the corpus buffers kept for `dev` (< 0: every device) go back to the
 // device allocator; returns the bytes freed.  Buffers a running call holds are not touched, and the
 // cached copy streams are kept for the process (a concurrent transfer may be using them)

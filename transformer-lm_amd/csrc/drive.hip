@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "drive.h"
+#include "utf8fix.h"
 
 namespace bpe {
 
@@ -715,7 +716,9 @@ size_t window_table_slots(const WordAccumulator& a, const WordAccumulator& b, si
 
 }  // namespace
 
-void counter_add_source(WordAccumulator& acc, const Source& src, size_t window_bytes) {
+void counter_add_source(WordAccumulator& acc, const Source& src, size_t window_bytes, int errors,
+                        bpe_utf8_stats* report) {
+    bpe_utf8_stats rep{0, 0, ~0ULL};
     const size_t window = std::max<size_t>(window_bytes ? window_bytes : kDefaultWindow, (size_t)64 << 10);
     int cur = 0;
     BPE_HIP(hipGetDevice(&cur));
@@ -739,12 +742,13 @@ void counter_add_source(WordAccumulator& acc, const Source& src, size_t window_b
     for (size_t k = 0; k < n_win; ++k) {
         const size_t off = cut[k], len = cut[k + 1] - off;
         Prepared pre;
-        DevBuf<uint8_t> scratch;
+        DevBuf<uint8_t> scratch, fixed;
         const uint8_t* text = d->b.p;
         size_t tn = len;
         WordCounts wc;
+        bool repair = false;
+        const auto t0 = std::chrono::steady_clock::now();
         try {
-            const auto t0 = std::chrono::steady_clock::now();
             if (load_and_count(src, off, len, d->b.p, dev, io_threads(), s, pre, window_table_slots(into, acc, len))) {
                 wc = std::move(pre.wc);
                 load_ms += pre.load_ms;
@@ -758,7 +762,21 @@ void counter_add_source(WordAccumulator& acc, const Source& src, size_t window_b
             }
         } catch (const Error& e) {
             (void)hipStreamSynchronize(s);
-            rethrow_at(e, off);
+            if (!errors || e.code != BPE_E_UTF8) rethrow_at(e, off);
+            repair = true;   // the window is resident (the error is raised once it is loaded whole)
+        }
+        if (repair) {
+            // non-strict: the partial table is gone with the failed count; repair the window into a
+            // buffer sized from the scan, then newlines and the count as in the \r branch.  Windows
+            // end at ASCII bytes, which end every unit: the windows' repairs are the file's.
+            const double loaded = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            bpe_utf8_stats ws{0, 0, ~0ULL};
+            text = repair_text(d->b.p, len, errors, fixed, &tn, &ws, s);
+            utf8_stats_add(rep, ws, off);
+            if (tn) text = prepare_text(text, tn, scratch, &tn, s);
+            count_words(text, tn, wc, s, nullptr);
+            load_ms += loaded;
+            count_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - loaded;
         }
         BPE_HIP(hipStreamSynchronize(s));
         into.fold(text, wc, tn);   // returns once the buffer may take the next window
@@ -766,23 +784,34 @@ void counter_add_source(WordAccumulator& acc, const Source& src, size_t window_b
     }
     into.note_input(n_bytes, n_win, max_win, load_ms, count_ms);
     if (tmp) acc.absorb(*tmp);
+    if (report) *report = rep;
 }
 
-void counter_add_device(WordAccumulator& acc, const uint8_t* d_data, size_t n, hipStream_t stream) {
+void counter_add_device(WordAccumulator& acc, const uint8_t* d_data, size_t n, hipStream_t stream, int errors,
+                        bpe_utf8_stats* report) {
     int cur = 0;
     BPE_HIP(hipGetDevice(&cur));
     struct DevGuard { int prev; ~DevGuard() { (void)hipSetDevice(prev); } } dg{cur};
     BPE_HIP(hipSetDevice(acc.device()));
     const hipStream_t s = stream ? stream : acc.stream();
     const auto t0 = std::chrono::steady_clock::now();
-    DevBuf<uint8_t> scratch;
+    DevBuf<uint8_t> scratch, fixed;
     size_t tn = 0;
-    const uint8_t* text = prepare_text(d_data, n, scratch, &tn, s);
+    bpe_utf8_stats rep{0, 0, ~0ULL};
+    const uint8_t* text = nullptr;
+    try {
+        text = prepare_text(d_data, n, scratch, &tn, s);
+    } catch (const Error& e) {
+        if (!errors || e.code != BPE_E_UTF8) throw;
+        text = repair_text(d_data, n, errors, fixed, &tn, &rep, s);
+        if (tn) text = prepare_text(text, tn, scratch, &tn, s);
+    }
     WordCounts wc;
     count_words(text, tn, wc, s, nullptr);
     BPE_HIP(hipStreamSynchronize(s));
     const double count_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     acc.fold(text, wc, tn);
+    if (report) *report = rep;
     acc.note_input(tn, 1, n, 0, count_ms);
 }
 

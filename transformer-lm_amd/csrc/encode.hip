@@ -56,6 +56,7 @@
 #include "pretok.h"
 #include "stage.h"
 #include "stage2.h"
+#include "utf8fix.h"
 
 namespace bpe {
 namespace {
@@ -1560,6 +1561,12 @@ struct bpe_tokenizer {
     std::string vblob, mblob;
     std::vector<std::string> sp_in;
     int device = 0;
+    // ill-formed UTF-8 in bpe_tok_encode_files (bpe_tok_set_errors): the mode, and what the last
+    // call repaired (the totals, the file of the first span, the spans per file)
+    int errors = 0;
+    bpe_utf8_stats fix_total{0, 0, ~0ULL};
+    uint64_t fix_first_file = 0;
+    std::vector<uint64_t> fix_file_units;
     std::mutex copies_m;
     std::vector<std::pair<long long, std::unique_ptr<bpe_tokenizer>>> copies;   // (rank << 8 | device)
     ~bpe_tokenizer() {
@@ -2801,15 +2808,28 @@ void encode_files_pipelined(bpe_tokenizer& T, const char* const* paths, size_t n
                 const size_t nin = hold_prev + w.len - hold;
                 size_t mlen = 0;
                 DevBuf<uint8_t> nl;   // the translated copy of a window that holds a \r
+                DevBuf<uint8_t> fixed;   // the repaired copy of a range that fails validation (non-strict)
                 const uint8_t* t = nullptr;
                 try {
                     t = prepare_text(in, nin, nl, &mlen, s);
                 } catch (const Error& e) {
                     const size_t p = e.msg.find("position ");
                     if (e.code != BPE_E_UTF8 || p == std::string::npos) throw;
-                    throw Error{BPE_E_UTF8, "'utf-8' codec can't decode byte at position " +
-                                                std::to_string(std::stoull(e.msg.substr(p + 9)) + (w.off - hold_prev)) +
-                                                " of " + paths[w.file]};
+                    if (!T.errors)
+                        throw Error{BPE_E_UTF8, "'utf-8' codec can't decode byte at position " +
+                                                    std::to_string(std::stoull(e.msg.substr(p + 9)) + (w.off - hold_prev)) +
+                                                    " of " + paths[w.file]};
+                    // The range ends where bpe_window_holdback cut it: what is held back is a proper
+                    // prefix of a well-formed sequence, a unit that could still grow, and every unit
+                    // before it is decided whatever follows.  So the ranges' repairs are the file's.
+                    bpe_utf8_stats ws{0, 0, ~0ULL};
+                    size_t fn = 0;
+                    t = repair_text(in, nin, T.errors, fixed, &fn, &ws, s);
+                    if (T.fix_total.first == ~0ULL && ws.first != ~0ULL) T.fix_first_file = w.file;
+                    utf8_stats_add(T.fix_total, ws, w.off - hold_prev);
+                    T.fix_file_units[w.file] += ws.n_units;
+                    mlen = fn;
+                    if (fn) t = prepare_text(t, fn, nl, &mlen, s);
                 }
                 if (D.text.n < carry + mlen + 64) {   // a piece longer than the buffer: grow, keep the carry
                     DevBuf<uint8_t> nb(carry + mlen + 64);
@@ -3054,6 +3074,9 @@ int bpe_tok_encode_files(bpe_tokenizer* tok, const char* const* paths, size_t n_
         BPE_REQUIRE(!id_counts || (n_counts > 0 && n_counts <= (1ull << 32)), BPE_E_ARG, "bad id table size");
         for (size_t i = 0; i < n_paths; ++i) BPE_REQUIRE(paths[i], BPE_E_ARG, "NULL path");
         bpe_dataset_stats st{};
+        tok->fix_total = bpe_utf8_stats{0, 0, ~0ULL};
+        tok->fix_first_file = 0;
+        tok->fix_file_units.assign(n_paths, 0);
         if (file_id_offsets) std::fill(file_id_offsets, file_id_offsets + n_paths + 1, (uint64_t)0);
         if (id_counts) std::fill(id_counts, id_counts + n_counts, (uint64_t)0);
         TmpFile out, idx;
@@ -3081,6 +3104,25 @@ int bpe_tok_encode_files(bpe_tokenizer* tok, const char* const* paths, size_t n_
         bpe::set_error(BPE_E_NOMEM, "host allocation failed");
         return BPE_E_NOMEM;
     }
+}
+
+int bpe_tok_set_errors(bpe_tokenizer* tok, int mode) {
+    return bpe::guarded_enc([&] {
+        BPE_REQUIRE(tok, BPE_E_ARG, "NULL argument");
+        BPE_REQUIRE(mode >= BPE_UTF8_STRICT && mode <= BPE_UTF8_IGNORE, BPE_E_ARG,
+                    "mode must be 0 (strict), 1 (replace) or 2 (ignore)");
+        tok->errors = mode;
+    });
+}
+
+int bpe_tok_utf8_report(const bpe_tokenizer* tok, bpe_utf8_stats* total, uint64_t* first_file, uint64_t* file_units,
+                        size_t n_files) {
+    return bpe::guarded_enc([&] {
+        BPE_REQUIRE(tok && (n_files == 0 || file_units), BPE_E_ARG, "NULL argument");
+        if (total) *total = tok->fix_total;
+        if (first_file) *first_file = tok->fix_first_file;
+        for (size_t i = 0; i < n_files; ++i) file_units[i] = i < tok->fix_file_units.size() ? tok->fix_file_units[i] : 0;
+    });
 }
 
 int bpe_tok_encode_chunks(bpe_tokenizer* tok, const uint8_t* utf8, size_t n, const uint64_t* starts,
