@@ -290,6 +290,29 @@ int bpe_tok_encode_batch(bpe_tokenizer* tok, const uint8_t* utf8, size_t n, cons
 int bpe_tok_encode_batch_device(bpe_tokenizer* tok, const uint8_t* d_utf8, size_t n, const uint64_t* doc_starts,
                                 size_t n_docs, uint32_t* d_out, size_t* n_out, uint64_t* d_id_offsets,
                                 void* hip_stream);
+/* Encode with offsets: the batch encode above, and for every id the half-open span (start, end) of
+ * the text it came from, relative to the start of its own document: spans[2 i], spans[2 i + 1]
+ * for id i.  unit 0: bytes -- text[start:end) are the bytes of the merge piece that produced the
+ * id (a special token: its own bytes, whether or not the vocab had it).  A pre-token equal to a
+ * special yields no id, so the next span starts past it; otherwise the spans of a document tile
+ * it, in order and without overlap.  unit 1: characters -- with C(p) = the bytes of text[0:p)
+ * that are not continuation bytes (b & 0xC0 != 0x80), start = C(start) - (1 if text[start] is a
+ * continuation byte), end = C(end): a byte-level token that begins or ends inside a character
+ * covers that character.  Any other unit: BPE_E_ARG.  The text is valid UTF-8 (every document on
+ * its own).  Limits: a document of 2^32 bytes or more is BPE_E_LIMIT; a vocab in which one id
+ * names byte strings of different lengths has no per-id length, and both calls refuse it with
+ * BPE_E_ARG (decided at bpe_tok_create; the other encode calls are unaffected).  cap >= n and
+ * spans_cap >= n (in spans, 8 bytes each) always suffice. */
+int bpe_tok_encode_spans(bpe_tokenizer* tok, const uint8_t* utf8, size_t n, const uint64_t* doc_starts,
+                         size_t n_docs, int unit, uint32_t* ids_out, size_t cap, size_t* n_out,
+                         uint64_t* id_offsets_out, uint32_t* spans_out, size_t spans_cap);
+/* same, device-resident text, ids (d_ids holds >= n), offsets (n_docs + 1) and spans (d_spans holds
+ * >= n spans of two uint32 and is 8-byte aligned); doc_starts in host memory.  One call at a time
+ * per tokenizer, on the current device, as the batch calls; the scratch it adds is released by
+ * bpe_tok_release_buffers. */
+int bpe_tok_encode_spans_device(bpe_tokenizer* tok, const uint8_t* d_utf8, size_t n, const uint64_t* doc_starts,
+                                size_t n_docs, int unit, uint32_t* d_ids, size_t* n_out, uint64_t* d_id_offsets,
+                                uint32_t* d_spans, void* hip_stream);
 /* CSR ids (as the batch encode returns them) -> a dense [n_rows, row_len] matrix of int32
  * (elem_bytes 4) or int64 (8) in d_out, and d_lengths[i] = min(L_i, row_len).  A row longer than
  * row_len keeps its first ids (flags & 1: its last); a shorter one is filled with pad on the

@@ -225,6 +225,122 @@ class Tokenizer:
                                               sp), "pack rows")
         return out, lengths
 
+    # ------------------------------------------------------------------ encode with offsets
+    # The batch encode, and for every id the half-open span of its document's text that produced
+    # it (bpe_tok_encode_spans): unit="byte" indexes text.encode("utf-8"), unit="char" (the
+    # default: callers hold str) indexes the str.  A leading space belongs to its token; a special
+    # token's span is the special; a pre-token equal to a special yields no id, so the next span
+    # starts past it.  A byte-level token that begins or ends inside a character covers that
+    # character, so text[s:e].encode() always contains the token's bytes.  The ids are those of
+    # encode() / encode_batch().  A vocab in which one id names byte strings of different lengths
+    # has no per-id length: ValueError.  On the current device, like the batch encode.
+    _UNITS = {"byte": 0, "char": 1}
+
+    @classmethod
+    def _unit(cls, unit) -> int:
+        if not isinstance(unit, str) or unit not in cls._UNITS:
+            raise ValueError("unit is 'byte' or 'char'")
+        return cls._UNITS[unit]
+
+    @staticmethod
+    def _span_status(rc: int, what: str) -> None:
+        if rc == _lib.BPE_E_ARG:
+            raise ValueError((_lib.lib().bpe_last_error() or b"").decode("utf-8", "replace"))
+        _lib.check(rc, what)
+
+    def encode_batch_offsets_np(self, texts: List[str], unit: str = "char"):
+        """-> (ids np.uint32 [N], id_offsets np.int64 [len(texts) + 1], spans np.int64 [N, 2]):
+        document i's ids are ids[id_offsets[i]:id_offsets[i + 1]] and id j came from
+        texts[i][spans[j, 0]:spans[j, 1]] (unit="byte": from those bytes of its UTF-8).  One join,
+        one library call."""
+        import numpy as np
+        u = self._unit(unit)
+        texts = list(texts)
+        h = self._device()
+        data, starts = self._join(texts)
+        n, nd = len(data), len(texts)
+        ids = np.empty(max(n, 1), dtype=np.uint32)
+        spans = np.empty((max(n, 1), 2), dtype=np.uint32)
+        offsets = np.zeros(nd + 1, dtype=np.uint64)
+        n_out = ctypes.c_size_t(0)
+        if nd:
+            rc = _lib.lib().bpe_tok_encode_spans(h, data, n, starts.ctypes.data, nd, u, ids.ctypes.data, ids.size,
+                                                 ctypes.byref(n_out), offsets.ctypes.data, spans.ctypes.data,
+                                                 spans.shape[0])
+            self._span_status(rc, "encode_spans")
+        m = n_out.value
+        return ids[:m].copy(), offsets.astype(np.int64), spans[:m].astype(np.int64)
+
+    def encode_batch_offsets(self, texts: List[str], unit: str = "char"):
+        """-> [(encode(t), [(start, end), ...]) for t in texts] in one library call."""
+        ids, offsets, spans = self.encode_batch_offsets_np(texts, unit)
+        flat, off = ids.tolist(), offsets.tolist()
+        sp = [tuple(x) for x in spans.tolist()]
+        return [(flat[a:b], sp[a:b]) for a, b in zip(off, off[1:])]
+
+    def encode_with_offsets(self, text: str, unit: str = "char") -> Tuple[List[int], List[Tuple[int, int]]]:
+        """-> (encode(text), [(start, end) of every id])."""
+        ids, _, spans = self.encode_batch_offsets_np([text], unit)
+        return ids.tolist(), [tuple(x) for x in spans.tolist()]
+
+    def encode_batch_padded_offsets(self, texts: List[str], max_length: int | None = None, *, pad_id: int,
+                                    truncation: str = "right", padding_side: str = "right", dtype=None,
+                                    unit: str = "char"):
+        """encode_batch_padded with the spans: -> (ids [B, T], int32 lengths [B], spans [B, T, 2]
+        torch.int64), all on the current device; the ids and lengths are encode_batch_padded's, a
+        kept id's span stands at its position and a padding position holds (0, 0).  The ids and the
+        spans never leave the device (bpe_tok_encode_spans_device, then bpe_ids_pack_rows_device
+        for the ids and for each span column)."""
+        import torch
+        u = self._unit(unit)
+        dtype = torch.int64 if dtype is None else dtype
+        if truncation not in ("right", "left") or padding_side not in ("right", "left"):
+            raise ValueError("truncation and padding_side are 'right' or 'left'")
+        if dtype not in (torch.int32, torch.int64):
+            raise ValueError("dtype is torch.int32 or torch.int64")
+        if max_length is not None and max_length < 0:
+            raise ValueError("max_length is negative")
+        texts = list(texts)
+        h = self._device()
+        L = _lib.lib()
+        data, starts = self._join(texts)
+        n, nd = len(data), len(texts)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        lengths = torch.zeros(nd, dtype=torch.int32, device=dev)
+        if nd == 0:
+            T0 = max_length or 0
+            return (torch.empty((0, T0), dtype=dtype, device=dev), lengths,
+                    torch.empty((0, T0, 2), dtype=torch.int64, device=dev))
+        stream = torch.cuda.current_stream()
+        sp = ctypes.c_void_p(stream.cuda_stream)
+        d_ids = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        d_spans = torch.zeros((max(n, 1), 2), dtype=torch.int32, device=dev)
+        d_off = torch.zeros(nd + 1, dtype=torch.int64, device=dev)
+        if n:
+            d_text = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
+            stream.synchronize()
+            n_out = ctypes.c_size_t(0)
+            self._span_status(L.bpe_tok_encode_spans_device(
+                h, ctypes.c_void_p(d_text.data_ptr()), n, starts.ctypes.data, nd, u, ctypes.c_void_p(d_ids.data_ptr()),
+                ctypes.byref(n_out), ctypes.c_void_p(d_off.data_ptr()), ctypes.c_void_p(d_spans.data_ptr()), sp),
+                "encode_spans")
+        T = int((d_off[1:] - d_off[:-1]).max()) if max_length is None else int(max_length)
+        out = torch.empty((nd, T), dtype=dtype, device=dev)
+        flags = (1 if truncation == "left" else 0) | (2 if padding_side == "left" else 0)
+        cols = [d_spans[:, k].contiguous() for k in (0, 1)]   # (uint32 values in int32 storage)
+        packed = [torch.empty((nd, T), dtype=torch.int64, device=dev) for _ in cols]
+        scratch = torch.empty(nd, dtype=torch.int32, device=dev)
+        stream.synchronize()
+        _lib.check(L.bpe_ids_pack_rows_device(ctypes.c_void_p(d_ids.data_ptr()), ctypes.c_void_p(d_off.data_ptr()), nd,
+                                              T, int(pad_id), flags, 4 if dtype == torch.int32 else 8,
+                                              ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(lengths.data_ptr()),
+                                              sp), "pack rows")
+        for col, dst in zip(cols, packed):
+            _lib.check(L.bpe_ids_pack_rows_device(ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(d_off.data_ptr()), nd,
+                                                  T, 0, flags, 8, ctypes.c_void_p(dst.data_ptr()),
+                                                  ctypes.c_void_p(scratch.data_ptr()), sp), "pack rows")
+        return out, lengths, torch.stack(packed, dim=-1)
+
     def encode_iterable(self, iterable: Iterable[str]) -> Iterator[int]:
         """tokenizer.py:140-150: concatenate items until >= 2 MiB characters, encode each chunk."""
         it = iter(iterable)

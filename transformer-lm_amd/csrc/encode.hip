@@ -43,6 +43,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
@@ -507,6 +508,13 @@ struct ScanCuts {
     const uint32_t* chunk_cut0;       // n_chunks + 1: the first cut at or after each chunk's first byte
     uint32_t* cut_rec;                // per cut: record index inside its chunk's run
 };
+// The export of the span calls (encode with offsets), on top of the cuts': every record's first
+// byte, relative to its chunk (< kChunk, so 16 bits), at the record's index in an array parallel
+// to recs.
+struct ScanCutsPos : ScanCuts {
+    uint16_t* rec_pos;
+};
+static_assert(kChunk <= 65536, "a record's chunk-relative position fits 16 bits");
 
 // A workgroup appends its pending entries to a block of the pool it holds; a block is
 // chunk-sized (a chunk has at most one pre-token per byte), so a chunk that does not fit the
@@ -539,9 +547,11 @@ __device__ __forceinline__ uint32_t dict_rec(uint32_t rec, size_t cap) {
 #define BPE355_ENC_EARLY_PREFETCH 0
 #endif
 // kCuts: the instantiations of encode_batch also export every cut's record index (ScanCuts); in the
-// others C is never read.
-template <bool kAligned, bool kCuts>
-__global__ void __launch_bounds__(256, BPE355_ENC_SCAN_WG) k_enc_scan4(ScanArgs A, EncDict D, ScanCuts C) {
+// others C is never read.  kPos: the span calls' instantiations (always with kCuts) also export
+// every record's position (ScanCutsPos); the others take a plain ScanCuts and are unchanged.
+template <bool kAligned, bool kCuts, bool kPos = false>
+__global__ void __launch_bounds__(256, BPE355_ENC_SCAN_WG)
+k_enc_scan4(ScanArgs A, EncDict D, typename std::conditional<kPos, ScanCutsPos, ScanCuts>::type C) {
     __shared__ uint64_t s_mask[kWords];
     __shared__ unsigned long long c_key[kEncCache];
     __shared__ uint64_t c_lo[kEncCache], c_hi[kEncCache];
@@ -804,6 +814,7 @@ __global__ void __launch_bounds__(256, BPE355_ENC_SCAN_WG) k_enc_scan4(ScanArgs 
                         }
                     }
                 }
+                if constexpr (kPos) C.rec_pos[rbase + toff + k] = (uint16_t)r;
                 out[k++] = rec;
             }
         }
@@ -1382,6 +1393,281 @@ __global__ void k_enc_doc_offsets(const uint32_t* __restrict__ doc_cut, size_t n
     }
 }
 
+// ------------------------------------------------------------------ 5''. spans (encode with offsets)
+// For every id the half-open byte span, relative to its document, of the merge piece that
+// produced it.  The scan's kPos instantiations leave every record's first byte (ScanCutsPos); a
+// word's ids tile its bytes in order, so id j of a record starts at the record's position plus
+// the byte lengths of ids 0..j-1, and the length of an id is a property of the vocab: a table
+// built once per tokenizer (SpanLens).  A special's record takes sp_len instead (its id may be
+// shared with an ordinary entry), and a dropped pre-token (info 0) has bytes and no id, so the
+// next span starts past it.
+
+// id -> byte length, open addressing: an entry is id << 32 | (length + 1), 0 an empty slot
+struct SpanLens {
+    const unsigned long long* ent;
+    unsigned long long mask;   // slots - 1
+};
+__host__ __device__ inline size_t span_len_slot(uint32_t id, unsigned long long mask) {
+    return (size_t)(mix64((uint64_t)id + 1) & mask);
+}
+__device__ __forceinline__ uint32_t span_len_of(const SpanLens& L, uint32_t id) {
+    size_t sl = span_len_slot(id, L.mask);
+    for (;;) {
+        const unsigned long long e = L.ent[sl];
+        if (e == 0) return 0u;   // no such id: the sum check reports it
+        if ((uint32_t)(e >> 32) == id) return (uint32_t)e - 1u;
+        sl = (sl + 1) & L.mask;
+    }
+}
+
+// per chunk: the first byte of the first record after the chunk's own (the end of its last
+// record), n when there is none.  A chunk without a record lies inside one pre-token, which is
+// under 8 MiB, so the walk is short.
+__global__ void k_enc_chunk_next(const uint32_t* __restrict__ rec_n, const unsigned long long* __restrict__ rec_base,
+                                 const uint16_t* __restrict__ rec_pos, size_t n_chunks, unsigned long long n,
+                                 unsigned long long* __restrict__ next) {
+    for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < n_chunks; c += (size_t)gridDim.x * blockDim.x) {
+        unsigned long long e = n;
+        for (size_t d = c + 1; d < n_chunks; ++d)
+            if (rec_n[d]) {
+                e = (unsigned long long)d * kChunk + rec_pos[rec_base[d]];
+                break;
+            }
+        next[c] = e;
+    }
+}
+
+struct SpanArgs {
+    const uint16_t* rec_pos;             // per record: its first byte, relative to its chunk
+    const unsigned long long* next;      // per chunk: k_enc_chunk_next
+    const unsigned long long* cuts;      // the document starts inside the text: sorted, distinct
+    const uint32_t* chunk_cut0;          // n_chunks + 1: the first cut at or after each chunk's first byte
+    const uint32_t* sp_len;
+    SpanLens L;
+};
+constexpr unsigned kSpanStatus = 512u;   // status: a word's id lengths do not sum to its bytes
+
+// one record's spans through put(position, start, end), from position o; returns its ids.
+// pos / end: the record's bytes in the text; doc: its document's first byte.
+template <class Put>
+__device__ __forceinline__ uint32_t put_spans(const EmitArgs& A, const SpanArgs& P, uint32_t rec, unsigned long long info,
+                                              unsigned long long pos, unsigned long long end, unsigned long long doc,
+                                              uint32_t o, const Put& put) {
+    if (info == 0) return 0;
+    const uint32_t s0 = (uint32_t)(pos - doc);   // a document is under 2^32 bytes (checked on the host)
+    if ((rec & kRecPendBit) && (rec & kRecKind3) == kRecSpecial) {
+        const uint32_t l = P.sp_len[rec & kRecPayload29];
+        if (pos + l != end) atomicOr(A.status, kSpanStatus);
+        put(o, s0, s0 + l);
+        return 1;
+    }
+    uint32_t cur = s0, nm;
+    if (info & kInlineIds) {
+        uint32_t ids[4];
+        nm = info_inline_ids(info, ids);
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j)
+            if (j < nm) {
+                const uint32_t l = span_len_of(P.L, ids[j]);
+                put(o + j, cur, cur + l);
+                cur += l;
+            }
+    } else {
+        nm = info_nids(info);
+        const uint32_t* src = ((info & kDictPool) ? A.D.pool : A.pool) + (info & kPoolOff);
+        for (uint32_t j = 0; j < nm; ++j) {
+            const uint32_t l = span_len_of(P.L, src[j]);
+            put(o + j, cur, cur + l);
+            cur += l;
+        }
+    }
+    if ((unsigned long long)(cur - s0) != end - pos) atomicOr(A.status, kSpanStatus);
+    return nm;
+}
+
+// The emit's write pass once more, for the spans: the same parts, the same coff and the same three
+// paths (LDS-staged, straight to memory when a part has more ids than LDS holds, rounds of 256
+// when it has more records than the registers hold).  It runs after the ids' write pass and
+// reads the infos that pass read; the ids-only kernels are not touched.  out: uint32_t[2] per id,
+// 8-byte aligned; the staged path stores two spans per 16-byte write after a one-span head.
+__global__ void __launch_bounds__(256) k_enc_emit_spans(EmitArgs A, SpanArgs P, unsigned long long n, uint2* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) uint2 buf[kEmitIds];
+    __shared__ uint32_t s_ws[4];
+    const int tid = threadIdx.x;
+    for (size_t c = blockIdx.x; c < A.n_chunks * kEmitParts; c += gridDim.x) {   // c: a part
+        const size_t ch = c / kEmitParts;
+        const unsigned part = (unsigned)(c % kEmitParts);
+        const uint32_t mc = A.rec_n[ch];
+        // (the emit's split of the chunk's records into parts)
+        const uint32_t r0 = (uint32_t)((unsigned long long)mc * part / kEmitParts),
+                       r1 = (uint32_t)((unsigned long long)mc * (part + 1) / kEmitParts);
+        const uint32_t m = r1 - r0;
+        const uint32_t* __restrict__ r = A.recs + A.rec_base[ch] + r0;
+        const uint16_t* __restrict__ rp = P.rec_pos + A.rec_base[ch] + r0;
+        const unsigned long long cbase = (unsigned long long)ch * kChunk;
+        const unsigned long long cnext = P.next[ch];
+        const uint32_t q0 = P.chunk_cut0[ch], q1 = P.chunk_cut0[ch + 1];
+        // record i of the part: its first byte, its end, its document's first byte
+        auto rec_pos = [&](uint32_t i) -> unsigned long long { return cbase + rp[i]; };
+        auto rec_end = [&](uint32_t i) -> unsigned long long { return r0 + i + 1 < mc ? cbase + rp[i + 1] : cnext; };
+        auto doc_of = [&](unsigned long long p) -> unsigned long long {
+            uint32_t lo = q0, hi = q1;   // the cuts of this chunk that are <= p: [q0, lo)
+            while (lo < hi) {
+                const uint32_t mid = lo + ((hi - lo) >> 1);
+                if (P.cuts[mid] <= p) lo = mid + 1;
+                else hi = mid;
+            }
+            return lo ? P.cuts[lo - 1] : 0ULL;
+        };
+        if (m <= 256u * kEmitR) {
+            const uint32_t R = (m + 255) >> 8;
+            const uint32_t lo = tid * R, hi = lo + R < m ? lo + R : m;
+            unsigned long long info[kEmitR];
+#pragma unroll
+            for (int i = 0; i < kEmitR; ++i) info[i] = lo + i < hi ? rec_info(A, r[lo + i]) : 0ULL;
+            uint32_t sum = 0;
+#pragma unroll
+            for (int i = 0; i < kEmitR; ++i) sum += lo + i < hi ? info_nids(info[i]) : 0u;
+            uint32_t T;
+            const uint32_t toff = block_excl_scan(sum, s_ws, &T);
+            const unsigned long long O = A.coff[c];
+            if (T <= kEmitIds) {
+                uint32_t o = toff;
+#pragma unroll
+                for (int i = 0; i < kEmitR; ++i)
+                    if (lo + i < hi) {
+                        const unsigned long long p = rec_pos(lo + i);
+                        o += put_spans(A, P, r[lo + i], info[i], p, rec_end(lo + i), doc_of(p), o,
+                                       [&](uint32_t q, uint32_t a, uint32_t b) { buf[q] = make_uint2(a, b); });
+                    }
+                __syncthreads();
+                const unsigned h = (((uintptr_t)(out + O) & 15) != 0 && T) ? 1u : 0u;
+                if (tid == 0 && h) out[O] = buf[0];
+                const unsigned body = (T - h) / 2;
+                uint4* dst = reinterpret_cast<uint4*>(out + O + h);
+                for (unsigned i = tid; i < body; i += 256) {
+                    const uint2 a = buf[h + 2 * i], b = buf[h + 2 * i + 1];
+                    dst[i] = make_uint4(a.x, a.y, b.x, b.y);
+                }
+                if (tid == 0 && h + 2 * body < T) out[O + T - 1] = buf[T - 1];
+                __syncthreads();   // buf is reused by the next part
+            } else {   // too many ids for LDS: straight to memory
+                uint32_t o = toff;
+#pragma unroll
+                for (int i = 0; i < kEmitR; ++i)
+                    if (lo + i < hi) {
+                        const unsigned long long p = rec_pos(lo + i);
+                        o += put_spans(A, P, r[lo + i], info[i], p, rec_end(lo + i), doc_of(p), o,
+                                       [&](uint32_t q, uint32_t a, uint32_t b) { out[O + q] = make_uint2(a, b); });
+                    }
+            }
+        } else {   // many records: rounds of 256
+            const unsigned long long O = A.coff[c];
+            uint32_t run = 0;
+            for (uint32_t b = 0; b < m; b += 256) {
+                const bool in = b + tid < m;
+                const unsigned long long inf = in ? rec_info(A, r[b + tid]) : 0ULL;
+                uint32_t rt;
+                const uint32_t off = block_excl_scan(in ? info_nids(inf) : 0u, s_ws, &rt);
+                if (in) {
+                    const unsigned long long p = rec_pos(b + tid);
+                    put_spans(A, P, r[b + tid], inf, p, rec_end(b + tid), doc_of(p), run + off,
+                              [&](uint32_t q, uint32_t a, uint32_t bb) { out[O + q] = make_uint2(a, bb); });
+                }
+                run += rt;
+            }
+        }
+    }
+    (void)n;
+}
+
+// ---- unit "char": byte spans -> character spans.  C(p) = the bytes of text[0, p) that are not
+// continuation bytes (b & 0xC0 != 0x80).  k_char_blocks counts them per 64-byte block of the
+// ADDRESS grid (block b = text positions [64 b - lead, 64 b - lead + 64), lead = the text
+// pointer's offset in its 64-byte line, so every load is aligned whatever the pointer), one
+// exclusive scan gives the blocks' prefix, and k_span_chars maps each span: start -> C(start) -
+// (1 if text[start] is a continuation byte), end -> C(end), both less C(document start).
+
+// the non-continuation bytes of a dword, one bit (bit 6) per byte
+__device__ __forceinline__ uint32_t noncont4(uint32_t w) {
+    const uint32_t x = (w & 0xC0C0C0C0u) ^ 0x80808080u;   // a continuation byte becomes 0
+    return (x | (x >> 1)) & 0x40404040u;
+}
+
+// a thread takes 16-byte units (aligned loads; a unit that the text only partly covers byte by
+// byte); four neighbouring lanes sum to one block
+__global__ void __launch_bounds__(256) k_char_blocks(const uint8_t* __restrict__ s, size_t n, size_t n_blocks,
+                                                     unsigned long long* __restrict__ cnt) {
+    const size_t lead = reinterpret_cast<uintptr_t>(s) & 63;
+    const uint8_t* const a0 = s - lead;
+    const size_t nv = n_blocks * 4;
+    const size_t S = (size_t)gridDim.x * blockDim.x;
+    for (size_t v0 = (size_t)blockIdx.x * blockDim.x; v0 < nv; v0 += S) {   // uniform over the workgroup
+        const size_t v = v0 + threadIdx.x;
+        uint32_t k = 0;
+        if (v < nv) {
+            const long long p0 = (long long)(16 * v) - (long long)lead;   // text position of byte 0
+            if (p0 >= 0 && p0 + 16 <= (long long)n) {
+                const uint4 q = *reinterpret_cast<const uint4*>(a0 + 16 * v);
+                k = __popc(noncont4(q.x)) + __popc(noncont4(q.y)) + __popc(noncont4(q.z)) + __popc(noncont4(q.w));
+            } else {
+                for (int j = 0; j < 16; ++j) {
+                    const long long p = p0 + j;
+                    if (p >= 0 && p < (long long)n) k += (s[p] & 0xC0u) != 0x80u;
+                }
+            }
+        }
+        k += __shfl_xor(k, 1);
+        k += __shfl_xor(k, 2);
+        if (v < nv && (v & 3) == 0) cnt[v >> 2] = k;
+    }
+}
+
+// C(p) for 0 <= p <= n: the block's prefix plus the non-continuation bytes of the block before p
+__device__ __forceinline__ unsigned long long char_index(const uint8_t* __restrict__ s, size_t n, size_t lead,
+                                                         const unsigned long long* __restrict__ pre, size_t n_blocks,
+                                                         unsigned long long p) {
+    const size_t b = (size_t)((p + lead) >> 6);
+    if (b >= n_blocks) return pre[n_blocks];   // p == n on a block boundary: the total
+    unsigned long long c = pre[b];
+    const long long bs = (long long)(b << 6) - (long long)lead;   // text position of the block's byte 0
+    // aligned 8-byte words of the block that lie wholly in [0, p); the rest byte by byte
+    long long q = bs < 0 ? 0 : bs;
+    for (; q < (long long)p && ((q + (long long)lead) & 7); ++q) c += (s[q] & 0xC0u) != 0x80u;
+    for (; q + 8 <= (long long)p; q += 8) {
+        const uint2 w = *reinterpret_cast<const uint2*>(s + q);
+        c += __popc(noncont4(w.x)) + __popc(noncont4(w.y));
+    }
+    for (; q < (long long)p; ++q) c += (s[q] & 0xC0u) != 0x80u;
+    (void)n;
+    return c;
+}
+
+// one thread per id: its document (the last one whose first id is at or before it), then both ends
+__global__ void __launch_bounds__(256) k_span_chars(const uint8_t* __restrict__ s, size_t n,
+                                                    const unsigned long long* __restrict__ pre, size_t n_blocks,
+                                                    const unsigned long long* __restrict__ id_off,
+                                                    const unsigned long long* __restrict__ doc_start, size_t n_docs,
+                                                    size_t n_ids, uint2* __restrict__ spans) {
+    const size_t lead = reinterpret_cast<uintptr_t>(s) & 63;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_ids; i += (size_t)gridDim.x * blockDim.x) {
+        size_t lo = 0, hi = n_docs - 1;   // the last document with id_off[d] <= i
+        while (lo < hi) {
+            const size_t mid = (lo + hi + 1) >> 1;
+            if (id_off[mid] <= i) lo = mid;
+            else hi = mid - 1;
+        }
+        const unsigned long long d0 = doc_start[lo];
+        const uint2 sp = spans[i];
+        const unsigned long long a = d0 + sp.x, e = d0 + sp.y;
+        const unsigned long long cd = char_index(s, n, lead, pre, n_blocks, d0);
+        unsigned long long ca = char_index(s, n, lead, pre, n_blocks, a);
+        if (a < n && (s[a] & 0xC0u) == 0x80u) --ca;
+        const unsigned long long ce = char_index(s, n, lead, pre, n_blocks, e);
+        spans[i] = make_uint2((uint32_t)(ca - cd), (uint32_t)(ce - cd));
+    }
+}
+
 // ------------------------------------------------------------------ 6. padded rows
 // CSR ids (u32 ids, u64 row offsets) -> a dense [n_rows, row_len] matrix of OutT (int32 / int64)
 // and the rows' kept lengths.  Flags as bpe_ids_pack_rows_device: a row longer than row_len keeps
@@ -1523,6 +1809,11 @@ struct bpe_tokenizer {
     bpe::DevBuf<bpe::DictEnt> dict_ent;
     bpe::DevBuf<uint32_t> dict_pool, byte_rec, dict_filt;
     size_t dict_slots = 0, dict_words = 0;
+    // the span calls' id -> byte length table (bpe::SpanLens); span_shared: some id names byte
+    // strings of different lengths, so the span calls are refused (decided once, at creation)
+    bpe::DevBuf<unsigned long long> span_len;
+    size_t span_slots = 0;
+    bool span_shared = false;
     // the per-pre-token record buffer, kept for the next call: freeing and re-allocating tens of
     // GB per call costs up to seconds in the driver (measured 0.5 -> 2.8 s for an 11.9 GB
     // encode).  Calls on one handle are serialized on its stream.
@@ -1547,6 +1838,10 @@ struct bpe_tokenizer {
         // encode_batch: per chunk its first cut, per cut its record index and id offset, per document its cut
         bpe::DevBuf<uint32_t> chunk_cut0, cut_rec, doc_cut;
         bpe::DevBuf<unsigned long long> cut_off;
+        // the span calls: per record its position, per chunk the end of its last record, the
+        // character counts of the text's 64-byte blocks and their prefix, the document starts
+        bpe::DevBuf<uint16_t> rec_pos;
+        bpe::DevBuf<unsigned long long> chunk_next, char_cnt, char_pre, doc_start;
         // the dataset encoder (encode_files_pipelined): the raw read ring, the translated text and
         // the buffer its carry moves through, the id ring, one region's separator positions, the
         // id table
@@ -1577,6 +1872,7 @@ struct bpe_tokenizer {
                               byte2tok.p, sp_bytes.p, sp_off.p, sp_len.p, sp_vid.p,
                               (int)specials.size()};
     }
+    bpe::SpanLens span_lens() const { return bpe::SpanLens{span_len.p, (unsigned long long)(span_slots - 1)}; }
     bpe::EncDict dict() const {
         return bpe::EncDict{dict_ent.p, (unsigned long long)(dict_slots - 1), dict_pool.p, byte_rec.p, dict_filt.p};
     }
@@ -1804,6 +2100,23 @@ void build_tokenizer(bpe_tokenizer& T, const uint8_t* vb, size_t vn, const uint8
     up(T.first_mask, fm);
     BPE_HIP(hipStreamSynchronize(T.stream));
     build_dictionary(T, intern, vid, b2t);
+    // the span calls' table: the byte length of every id the encoder can emit
+    size_t n_ids = 0;
+    for (const int64_t v : vid) n_ids += v >= 0;
+    T.span_slots = next_pow2(std::max<size_t>(64, 2 * n_ids));
+    std::vector<unsigned long long> sl(T.span_slots, 0ULL);
+    for (const auto& kv : intern) {
+        const int64_t v = vid[kv.second];
+        if (v < 0) continue;
+        const uint32_t id = (uint32_t)v;
+        const unsigned long long e = ((unsigned long long)id << 32) | (unsigned long long)(kv.first.size() + 1);
+        size_t q = span_len_slot(id, T.span_slots - 1);
+        while (sl[q] && (uint32_t)(sl[q] >> 32) != id) q = (q + 1) & (T.span_slots - 1);
+        if (sl[q] && sl[q] != e) T.span_shared = true;
+        sl[q] = e;
+    }
+    up(T.span_len, sl);
+    BPE_HIP(hipStreamSynchronize(T.stream));
 }
 
 // encode d_text[0..n) into d_out; returns the id count.  `cuts` (sorted byte offsets) make the
@@ -1817,16 +2130,23 @@ struct DocStarts {
     size_t n_docs;
     unsigned long long* d_out;     // device: n_docs + 1 entries
 };
+// `spans` (the span calls; with docs): d_spans gets every id's (start, end) in its document, in
+// bytes (unit 0) or characters (unit 1)
+struct SpanOut {
+    uint2* d_spans;                // device: one per id, 8-byte aligned
+    int unit;
+};
 
 template <class OutT>
 size_t encode_device(bpe_tokenizer& T, const uint8_t* d_text, size_t n, OutT* d_out,
                      hipStream_t s, const std::vector<unsigned long long>& cuts_in = {},
-                     const DocStarts* docs = nullptr) {
+                     const DocStarts* docs = nullptr, const SpanOut* spans = nullptr) {
     if (n == 0) return 0;
     std::vector<unsigned long long> cuts;
     for (unsigned long long c : cuts_in)
         if (c > 0 && c < n && (cuts.empty() || c > cuts.back())) cuts.push_back(c);
-    const bool want_cuts = docs && !cuts.empty();   // (no cut: every start is at byte 0 or at the end)
+    const bool want_pos = docs && spans;   // the scan exports the records' positions (with the cuts, if any)
+    const bool want_cuts = docs && (!cuts.empty() || want_pos);   // (no cut: every start is at byte 0 or at the end)
     if (docs) BPE_REQUIRE(cuts.size() < 0xFFFFFFF0ull, BPE_E_LIMIT, "too many documents for one encode");
     bool cuts_up = false;   // S.cuts holds the cuts
     EncTables E = T.tables();
@@ -1934,8 +2254,10 @@ size_t encode_device(bpe_tokenizer& T, const uint8_t* d_text, size_t n, OutT* d_
     const bool aligned = (reinterpret_cast<uintptr_t>(d_text) & 15u) == 0;
     auto kern = want_cuts ? (aligned ? k_enc_scan4<true, true> : k_enc_scan4<false, true>)
                           : (aligned ? k_enc_scan4<true, false> : k_enc_scan4<false, false>);
+    auto kern_pos = aligned ? k_enc_scan4<true, true, true> : k_enc_scan4<false, true, true>;
     int per_cu = 0, dev = 0, n_cu = 0;
-    BPE_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, kStage));
+    if (want_pos) BPE_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern_pos, 256, kStage));
+    else BPE_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, kStage));
     BPE_HIP(hipGetDevice(&dev));
     BPE_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
     unsigned sgrid = (unsigned)std::min<size_t>(n_chunks, (size_t)std::max(1, per_cu) * std::max(1, n_cu));
@@ -1985,8 +2307,8 @@ size_t encode_device(bpe_tokenizer& T, const uint8_t* d_text, size_t n, OutT* d_
     if (want_cuts) {   // the cuts on the device, and every chunk's first one
         const size_t nc = cuts.size();
         if (!cuts_up) {
-            S.cuts.reserve(nc);
-            to_device(S.cuts.p, cuts.data(), nc * 8, s);
+            S.cuts.reserve(std::max<size_t>(nc, 1));
+            if (nc) to_device(S.cuts.p, cuts.data(), nc * 8, s);
         }
         std::vector<uint32_t> first(n_chunks + 1);
         size_t j = 0;
@@ -1996,8 +2318,8 @@ size_t encode_device(bpe_tokenizer& T, const uint8_t* d_text, size_t n, OutT* d_
         }
         S.chunk_cut0.reserve(n_chunks + 1);
         to_device(S.chunk_cut0.p, first.data(), (n_chunks + 1) * 4, s);
-        S.cut_rec.reserve(nc);
-        S.cut_off.reserve(nc);
+        S.cut_rec.reserve(std::max<size_t>(nc, 1));
+        S.cut_off.reserve(std::max<size_t>(nc, 1));
         SC = ScanCuts{S.cuts.p, S.chunk_cut0.p, S.cut_rec.p};
     }
     const bool tracing = std::getenv("BPE355_TRACE") != nullptr;
@@ -2009,6 +2331,7 @@ size_t encode_device(bpe_tokenizer& T, const uint8_t* d_text, size_t n, OutT* d_
         kv.reserve(2 * cap);
         pos.reserve(cap);
         T.recs_cache.reserve(rec_cap);
+        if (want_pos) S.rec_pos.reserve(rec_cap);   // (every attempt rewrites it: the kept attempt's stays)
         BPE_HIP(hipMemsetAsync(kv.p, 0, 2 * cap * sizeof(unsigned long long), s));
         BPE_HIP(hipMemsetAsync(status.p, 0, 4, s));
         BPE_HIP(hipMemsetAsync(fill.p, 0, 8, s));
@@ -2018,7 +2341,14 @@ size_t encode_device(bpe_tokenizer& T, const uint8_t* d_text, size_t n, OutT* d_
                    cap - 1, (unsigned long long)(cap / 2), fill.p, T.recs_cache.p, rec_cap, rec_region, rec_fill.p,
                    rec_base.p, rec_n.p, pend_blocks ? S.pend.p : nullptr, pend_blocks, S.pend_nblk.p,
                    S.block_used.p, status.p};
-        hipLaunchKernelGGL(kern, dim3(sgrid), dim3(256), kStage, s, A, D, SC);
+        if (want_pos) {
+            ScanCutsPos SP;
+            static_cast<ScanCuts&>(SP) = SC;
+            SP.rec_pos = S.rec_pos.p;
+            hipLaunchKernelGGL(kern_pos, dim3(sgrid), dim3(256), kStage, s, A, D, SP);
+        } else {
+            hipLaunchKernelGGL(kern, dim3(sgrid), dim3(256), kStage, s, A, D, SC);
+        }
         BPE_HIP(hipGetLastError());
         unsigned nblk = 0;
         to_host(&nblk, S.pend_nblk.p, 4, s);
@@ -2196,6 +2526,35 @@ size_t encode_device(bpe_tokenizer& T, const uint8_t* d_text, size_t n, OutT* d_
         BPE_REQUIRE(!(st & 128u), BPE_E_LIMIT, "a token id does not fit np.uint16 (vocab larger than 65536)");
     const size_t total = last[0] + last[1];
     BPE_REQUIRE(total <= n, BPE_E_HIP, "encode produced more ids than input bytes");
+    if (want_pos && total) {   // the spans: one more pass over the records, then (unit 1) bytes -> characters
+        S.chunk_next.reserve(n_chunks);
+        hipLaunchKernelGGL(k_enc_chunk_next, dim3(grid_for(n_chunks, 256)), dim3(256), 0, s, rec_n.p, rec_base.p,
+                           S.rec_pos.p, n_chunks, (unsigned long long)n, S.chunk_next.p);
+        BPE_HIP(hipGetLastError());
+        const SpanArgs PA{S.rec_pos.p, S.chunk_next.p, S.cuts.p, S.chunk_cut0.p, E.sp_len, T.span_lens()};
+        int p_cu = 0;
+        BPE_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&p_cu, k_enc_emit_spans, 256, 0));
+        const unsigned pgrid = (unsigned)std::min<size_t>(n_parts, (size_t)std::max(1, p_cu) * std::max(1, n_cu) * 2);
+        hipLaunchKernelGGL(k_enc_emit_spans, dim3(pgrid), dim3(256), 0, s, EA, PA, (unsigned long long)n, spans->d_spans);
+        BPE_HIP(hipGetLastError());
+        to_host(&st, status.p, 4, s);
+        BPE_REQUIRE(!(st & kSpanStatus), BPE_E_HIP, "internal error: a word's id lengths do not sum to its bytes");
+        if (spans->unit == 1) {
+            const size_t lead = reinterpret_cast<uintptr_t>(d_text) & 63, n_blocks = (n + lead + 63) / 64;
+            S.char_cnt.reserve(n_blocks + 1);
+            S.char_pre.reserve(n_blocks + 1);
+            S.doc_start.reserve(docs->n_docs);
+            to_device(S.doc_start.p, docs->starts, docs->n_docs * 8, s);
+            BPE_HIP(hipMemsetAsync(S.char_cnt.p + n_blocks, 0, 8, s));
+            hipLaunchKernelGGL(k_char_blocks, dim3(std::min<unsigned>(grid_for(n_blocks * 4, 256), 8192)), dim3(256), 0, s,
+                               d_text, n, n_blocks, S.char_cnt.p);
+            BPE_HIP(hipGetLastError());
+            exclusive_sum(S.char_cnt.p, S.char_pre.p, n_blocks + 1, s, &S.tmp);
+            hipLaunchKernelGGL(k_span_chars, dim3(grid_for(total, 256)), dim3(256), 0, s, d_text, n, S.char_pre.p,
+                               n_blocks, docs->d_out, S.doc_start.p, docs->n_docs, total, spans->d_spans);
+            BPE_HIP(hipGetLastError());
+        }
+    }
     BPE_HIP(hipStreamSynchronize(s));
     return total;
 }
@@ -3181,6 +3540,61 @@ int bpe_tok_encode_batch(bpe_tokenizer* tok, const uint8_t* utf8, size_t n, cons
         const bpe::DocStarts docs{doc_starts, n_docs, d_off.p};
         const size_t m = bpe::encode_device(*tok, d_text.p, n, d_out.p, tok->stream, cuts, &docs);
         if (m) BPE_HIP(hipMemcpyAsync(ids_out, d_out.p, m * 4, hipMemcpyDeviceToHost, tok->stream));
+        BPE_HIP(hipMemcpyAsync(id_offsets_out, d_off.p, (n_docs + 1) * 8, hipMemcpyDeviceToHost, tok->stream));
+        BPE_HIP(hipStreamSynchronize(tok->stream));
+        *n_out = m;
+    });
+}
+
+int bpe_tok_encode_spans_device(bpe_tokenizer* tok, const uint8_t* d_utf8, size_t n, const uint64_t* doc_starts,
+                                size_t n_docs, int unit, uint32_t* d_ids, size_t* n_out, uint64_t* d_id_offsets,
+                                uint32_t* d_spans, void* hip_stream) {
+    return bpe::guarded_enc([&] {
+        BPE_REQUIRE(tok && n_out && d_id_offsets && (n == 0 || (d_utf8 && d_ids && d_spans)), BPE_E_ARG, "NULL argument");
+        BPE_REQUIRE(unit == 0 || unit == 1, BPE_E_ARG, "unit must be 0 (byte) or 1 (char)");
+        BPE_REQUIRE((reinterpret_cast<uintptr_t>(d_spans) & 7u) == 0, BPE_E_ARG, "d_spans must be 8-byte aligned");
+        BPE_REQUIRE(!tok->span_shared, BPE_E_ARG,
+                    "spans are not defined for this vocab: one id names byte strings of different lengths");
+        const std::vector<unsigned long long> cuts = bpe::batch_cuts(doc_starts, n_docs, n);
+        for (size_t i = 0; i < n_docs; ++i)
+            BPE_REQUIRE(((i + 1 < n_docs ? doc_starts[i + 1] : (uint64_t)n) - doc_starts[i]) >> 32 == 0, BPE_E_LIMIT,
+                        "a document of 2^32 bytes or more: its spans do not fit uint32");
+        hipStream_t s = hip_stream ? (hipStream_t)hip_stream : tok->stream;
+        *n_out = 0;
+        if (n == 0) {   // empty documents only: every offset is 0, no span
+            BPE_HIP(hipMemsetAsync(d_id_offsets, 0, (n_docs + 1) * sizeof(uint64_t), s));
+            BPE_HIP(hipStreamSynchronize(s));
+            return;
+        }
+        const bpe::DocStarts docs{doc_starts, n_docs, reinterpret_cast<unsigned long long*>(d_id_offsets)};
+        const bpe::SpanOut so{reinterpret_cast<uint2*>(d_spans), unit};
+        *n_out = bpe::encode_device(*tok, d_utf8, n, d_ids, s, cuts, &docs, &so);
+    });
+}
+
+int bpe_tok_encode_spans(bpe_tokenizer* tok, const uint8_t* utf8, size_t n, const uint64_t* doc_starts, size_t n_docs,
+                         int unit, uint32_t* ids_out, size_t cap, size_t* n_out, uint64_t* id_offsets_out,
+                         uint32_t* spans_out, size_t spans_cap) {
+    return bpe::guarded_enc([&] {
+        BPE_REQUIRE(tok && n_out && id_offsets_out && (n == 0 || (utf8 && ids_out && spans_out)), BPE_E_ARG,
+                    "NULL argument");
+        BPE_REQUIRE(cap >= n && spans_cap >= n, BPE_E_ARG, "ids_out and spans_out capacities must be >= input bytes");
+        BPE_REQUIRE(unit == 0 || unit == 1, BPE_E_ARG, "unit must be 0 (byte) or 1 (char)");
+        *n_out = 0;
+        bpe::DevBuf<uint8_t> d_text(n);
+        bpe::DevBuf<uint32_t> d_out(n);
+        bpe::DevBuf<uint2> d_spans(n);
+        bpe::DevBuf<unsigned long long> d_off(n_docs + 1);
+        if (n) BPE_HIP(hipMemcpyAsync(d_text.p, utf8, n, hipMemcpyHostToDevice, tok->stream));
+        size_t m = 0;
+        const int rc = bpe_tok_encode_spans_device(tok, d_text.p, n, doc_starts, n_docs, unit, d_out.p, &m,
+                                                   reinterpret_cast<uint64_t*>(d_off.p),
+                                                   reinterpret_cast<uint32_t*>(d_spans.p), tok->stream);
+        if (rc != BPE_OK) throw bpe::Error{rc, bpe_last_error()};
+        if (m) {
+            BPE_HIP(hipMemcpyAsync(ids_out, d_out.p, m * 4, hipMemcpyDeviceToHost, tok->stream));
+            BPE_HIP(hipMemcpyAsync(spans_out, d_spans.p, m * 8, hipMemcpyDeviceToHost, tok->stream));
+        }
         BPE_HIP(hipMemcpyAsync(id_offsets_out, d_off.p, (n_docs + 1) * 8, hipMemcpyDeviceToHost, tok->stream));
         BPE_HIP(hipStreamSynchronize(tok->stream));
         *n_out = m;
