@@ -313,6 +313,33 @@ int bpe_tok_encode_spans(bpe_tokenizer* tok, const uint8_t* utf8, size_t n, cons
 int bpe_tok_encode_spans_device(bpe_tokenizer* tok, const uint8_t* d_utf8, size_t n, const uint64_t* doc_starts,
                                 size_t n_docs, int unit, uint32_t* d_ids, size_t* n_out, uint64_t* d_id_offsets,
                                 uint32_t* d_spans, void* hip_stream);
+/* Encode with BPE-dropout (Provilkov et al., 2020): the batch encode above, except that while a
+ * pre-token is merged every candidate merge is skipped with probability thr / 2^24.  Segmentation
+ * on specials, pre-tokenization, the dropping of a pre-token equal to a special and the id lookup
+ * (BPE_E_KEY) are those of bpe_tok_encode; a special yields its one id and draws nothing.  The draws
+ * are counter-based (mix64: z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27,
+ * z *= 0x94D049BB133111EB, z ^ z >> 31, all mod 2^64):
+ *     wk      = mix64(mix64(mix64(seed + 0x9E3779B97F4A7C15) ^ doc_key) ^ off)
+ *     dropped = (mix64(wk ^ (round << 32 | pos)) >> 40) < thr
+ * off: the byte offset of the pre-token's first byte in its document; round 0, 1, ...: the merge
+ * rounds of that pre-token; pos: the byte offset, inside the pre-token, of the pair's left token.
+ * A round merges, left to right, every occurrence that is not dropped of the ranked pair of lowest
+ * rank among the positions not dropped; when there is none the pre-token is done, also when
+ * ranked pairs remain.  Document i of the call draws with doc_key = doc_base + i, so a document's
+ * ids depend on (seed, doc_key, text) alone: not on the batch it is in, nor on the device's order
+ * of work or the pointers' alignment.  thr 0 is bpe_tok_encode_batch exactly; thr 2^24 gives every
+ * byte its own id; thr > 2^24 or doc_base + n_docs past 2^64: BPE_E_ARG.  (thr = round(p * 2^24)
+ * is computed by the caller: no float crosses the ABI.)  Limits: a document of 2^32 bytes or more,
+ * a pre-token of 8 MiB or more: BPE_E_LIMIT.  cap >= n always suffices. */
+int bpe_tok_encode_dropout(bpe_tokenizer* tok, const uint8_t* utf8, size_t n, const uint64_t* doc_starts,
+                           size_t n_docs, uint32_t thr, uint64_t seed, uint64_t doc_base, uint32_t* ids_out,
+                           size_t cap, size_t* n_out, uint64_t* id_offsets_out);
+/* same, device-resident text, ids (d_ids holds >= n; the call also uses it as scratch) and offsets
+ * (n_docs + 1); doc_starts in host memory.  One call at a time per tokenizer, on the current device,
+ * as the batch calls; the scratch it adds is released by bpe_tok_release_buffers. */
+int bpe_tok_encode_dropout_device(bpe_tokenizer* tok, const uint8_t* d_utf8, size_t n, const uint64_t* doc_starts,
+                                  size_t n_docs, uint32_t thr, uint64_t seed, uint64_t doc_base, uint32_t* d_ids,
+                                  size_t* n_out, uint64_t* d_id_offsets, void* hip_stream);
 /* CSR ids (as the batch encode returns them) -> a dense [n_rows, row_len] matrix of int32
  * (elem_bytes 4) or int64 (8) in d_out, and d_lengths[i] = min(L_i, row_len).  A row longer than
  * row_len keeps its first ids (flags & 1: its last); a shorter one is filled with pad on the

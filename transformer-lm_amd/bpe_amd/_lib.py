@@ -170,6 +170,10 @@ _SIGS = [
                                             _P, _SZ]),
     ("bpe_tok_encode_spans_device", ctypes.c_int, [_P, _P, _SZ, _P, _SZ, ctypes.c_int, _P, ctypes.POINTER(_SZ), _P,
                                                    _P, _P]),
+    ("bpe_tok_encode_dropout", ctypes.c_int, [_P, _U8P, _SZ, _P, _SZ, ctypes.c_uint32, ctypes.c_uint64,
+                                              ctypes.c_uint64, _P, _SZ, ctypes.POINTER(_SZ), _P]),
+    ("bpe_tok_encode_dropout_device", ctypes.c_int, [_P, _P, _SZ, _P, _SZ, ctypes.c_uint32, ctypes.c_uint64,
+                                                     ctypes.c_uint64, _P, ctypes.POINTER(_SZ), _P, _P]),
     ("bpe_ids_pack_rows_device", ctypes.c_int, [_P, _P, _SZ, _SZ, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                                 _P, _P, _P]),
     ("bpe_tok_encode_file_u16", ctypes.c_int, [_P, ctypes.c_char_p, _SZ, _P, _SZ, ctypes.POINTER(_SZ),

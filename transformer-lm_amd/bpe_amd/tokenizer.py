@@ -341,6 +341,106 @@ class Tokenizer:
                                                   ctypes.c_void_p(scratch.data_ptr()), sp), "pack rows")
         return out, lengths, torch.stack(packed, dim=-1)
 
+    # ------------------------------------------------------------------ encode with BPE-dropout
+    # The batch encode with subword regularisation (Provilkov et al., 2020; HF tokenizers'
+    # BPE(dropout=p)): while a pre-token is merged, every candidate merge is skipped with
+    # probability p.  The draws are counter-based (bpe_tok_encode_dropout in include/bpe355.h), so
+    # the ids of a document depend only on (seed, doc_key, text) -- not on the batch it is in: row
+    # i of a batch draws with doc_key = doc_base + i.  p = 0 is encode(); p = 1 gives every byte
+    # its own id.  Specials, the pre-tokenization and KeyError are encode()'s.  On the current
+    # device, like the batch encode.
+    _U64 = 1 << 64
+
+    @classmethod
+    def _dropout_args(cls, p, seed, key, n_docs: int = 0):
+        """-> thr = round(p * 2^24); ValueError unless p is a real in [0, 1] and seed, key and
+        key + n_docs are ints in [0, 2^64)."""
+        import numbers
+        if isinstance(p, bool) or not isinstance(p, numbers.Real) or not 0 <= p <= 1:   # (a NaN fails the comparison)
+            raise ValueError("p is a real number in [0, 1]")
+        for name, v in (("seed", seed), ("doc_key / doc_base", key)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 <= int(v) < cls._U64:
+                raise ValueError(f"{name} is an int in [0, 2^64)")
+        if int(key) + n_docs >= cls._U64:
+            raise ValueError("doc_base + len(texts) is below 2^64")
+        return int(round(float(p) * (1 << 24)))
+
+    def encode_batch_dropout_np(self, texts: List[str], p: float, seed: int, doc_base: int = 0):
+        """-> (ids np.uint32 [total], offsets np.int64 [len(texts) + 1]) as encode_batch_np, each
+        candidate merge skipped with probability p; document i draws with (seed, doc_base + i)."""
+        import numpy as np
+        texts = list(texts)
+        thr = self._dropout_args(p, seed, doc_base, len(texts))
+        h = self._device()
+        data, starts = self._join(texts)
+        n, nd = len(data), len(texts)
+        ids = np.empty(max(n, 1), dtype=np.uint32)
+        offsets = np.zeros(nd + 1, dtype=np.uint64)
+        n_out = ctypes.c_size_t(0)
+        if nd:
+            rc = _lib.lib().bpe_tok_encode_dropout(h, data, n, starts.ctypes.data, nd, thr, int(seed), int(doc_base),
+                                                   ids.ctypes.data, ids.size, ctypes.byref(n_out), offsets.ctypes.data)
+            _lib.check(rc, "encode_dropout")
+        return ids[:n_out.value].copy(), offsets.astype(np.int64)
+
+    def encode_batch_dropout(self, texts: List[str], p: float, seed: int, doc_base: int = 0) -> List[List[int]]:
+        """[encode_dropout(t, p, seed, doc_base + i) for i, t in enumerate(texts)] in one library call."""
+        ids, offsets = self.encode_batch_dropout_np(texts, p, seed, doc_base)
+        flat, off = ids.tolist(), offsets.tolist()
+        return [flat[a:b] for a, b in zip(off, off[1:])]
+
+    def encode_dropout(self, text: str, p: float, seed: int, doc_key: int = 0) -> List[int]:
+        """encode(text) with BPE-dropout: the ids depend on (seed, doc_key, text) alone."""
+        self._dropout_args(p, seed, doc_key, 1)
+        return self.encode_batch_dropout_np([text], p, seed, doc_key)[0].tolist()
+
+    def encode_batch_padded_dropout(self, texts: List[str], max_length: int | None = None, *, pad_id: int, p: float,
+                                    seed: int, doc_base: int = 0, truncation: str = "right",
+                                    padding_side: str = "right", dtype=None):
+        """encode_batch_padded with BPE-dropout: -> (tensor [len(texts), T], int32 lengths), both on
+        the current device, row i the ids of encode_dropout(texts[i], p, seed, doc_base + i).  The
+        text goes to the device once and the ids never leave it (bpe_tok_encode_dropout_device,
+        then bpe_ids_pack_rows_device)."""
+        texts = list(texts)
+        thr = self._dropout_args(p, seed, doc_base, len(texts))
+        if truncation not in ("right", "left") or padding_side not in ("right", "left"):
+            raise ValueError("truncation and padding_side are 'right' or 'left'")
+        if max_length is not None and max_length < 0:
+            raise ValueError("max_length is negative")
+        import torch
+        dtype = torch.int64 if dtype is None else dtype
+        if dtype not in (torch.int32, torch.int64):
+            raise ValueError("dtype is torch.int32 or torch.int64")
+        h = self._device()
+        L = _lib.lib()
+        data, starts = self._join(texts)
+        n, nd = len(data), len(texts)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        lengths = torch.zeros(nd, dtype=torch.int32, device=dev)
+        if nd == 0:
+            return torch.empty((0, max_length or 0), dtype=dtype, device=dev), lengths
+        stream = torch.cuda.current_stream()
+        sp = ctypes.c_void_p(stream.cuda_stream)
+        d_ids = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        d_off = torch.zeros(nd + 1, dtype=torch.int64, device=dev)
+        if n:
+            d_text = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
+            stream.synchronize()
+            n_out = ctypes.c_size_t(0)
+            _lib.check(L.bpe_tok_encode_dropout_device(h, ctypes.c_void_p(d_text.data_ptr()), n, starts.ctypes.data, nd,
+                                                       thr, int(seed), int(doc_base), ctypes.c_void_p(d_ids.data_ptr()),
+                                                       ctypes.byref(n_out), ctypes.c_void_p(d_off.data_ptr()), sp),
+                       "encode_dropout")
+        T = int((d_off[1:] - d_off[:-1]).max()) if max_length is None else int(max_length)
+        out = torch.empty((nd, T), dtype=dtype, device=dev)
+        flags = (1 if truncation == "left" else 0) | (2 if padding_side == "left" else 0)
+        stream.synchronize()
+        _lib.check(L.bpe_ids_pack_rows_device(ctypes.c_void_p(d_ids.data_ptr()), ctypes.c_void_p(d_off.data_ptr()), nd,
+                                              T, int(pad_id), flags, 4 if dtype == torch.int32 else 8,
+                                              ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(lengths.data_ptr()),
+                                              sp), "pack rows")
+        return out, lengths
+
     def encode_iterable(self, iterable: Iterable[str]) -> Iterator[int]:
         """tokenizer.py:140-150: concatenate items until >= 2 MiB characters, encode each chunk."""
         it = iter(iterable)

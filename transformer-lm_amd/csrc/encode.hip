@@ -28,6 +28,8 @@
 //      starts there; k_enc_cut_offsets turns those into id offsets with one more pass over the
 //      records, k_enc_doc_offsets hands every document its own.
 //   6. k_pack_rows: ids and offsets -> padded rows.
+//   (encode with dropout) steps 1 and 2 only, the scan in its kCuts, kPos instantiation; every
+//      occurrence then merges on its own in dropout.hip (dropout_emit), which reads the records.
 
 #include <algorithm>
 #include <cmath>
@@ -1842,6 +1844,7 @@ struct bpe_tokenizer {
         // character counts of the text's 64-byte blocks and their prefix, the document starts
         bpe::DevBuf<uint16_t> rec_pos;
         bpe::DevBuf<unsigned long long> chunk_next, char_cnt, char_pre, doc_start;
+        bpe::DropScratch drop;   // encode with dropout (dropout.hip)
         // the dataset encoder (encode_files_pipelined): the raw read ring, the translated text and
         // the buffer its carry moves through, the id ring, one region's separator positions, the
         // id table
@@ -2140,12 +2143,13 @@ struct SpanOut {
 template <class OutT>
 size_t encode_device(bpe_tokenizer& T, const uint8_t* d_text, size_t n, OutT* d_out,
                      hipStream_t s, const std::vector<unsigned long long>& cuts_in = {},
-                     const DocStarts* docs = nullptr, const SpanOut* spans = nullptr) {
+                     const DocStarts* docs = nullptr, const SpanOut* spans = nullptr, const DropParams* drop = nullptr) {
     if (n == 0) return 0;
     std::vector<unsigned long long> cuts;
     for (unsigned long long c : cuts_in)
         if (c > 0 && c < n && (cuts.empty() || c > cuts.back())) cuts.push_back(c);
-    const bool want_pos = docs && spans;   // the scan exports the records' positions (with the cuts, if any)
+    // the scan exports the records' positions (with the cuts, if any): the span calls and encode with dropout
+    const bool want_pos = docs && (spans || drop);
     const bool want_cuts = docs && (!cuts.empty() || want_pos);   // (no cut: every start is at byte 0 or at the end)
     if (docs) BPE_REQUIRE(cuts.size() < 0xFFFFFFF0ull, BPE_E_LIMIT, "too many documents for one encode");
     bool cuts_up = false;   // S.cuts holds the cuts
@@ -2355,7 +2359,7 @@ size_t encode_device(bpe_tokenizer& T, const uint8_t* d_text, size_t n, OutT* d_
         nblk = std::min(nblk, pend_blocks);
         pend_entries = (unsigned long long)nblk * kPendBlock;
         if (tracing) BPE_HIP(hipMemsetAsync(S.rstats.p, 0, 3 * sizeof(unsigned long long), s));
-        if (nblk) {   // the pending words, resolved in place
+        if (nblk && !drop) {   // the pending words, resolved in place (dropout reads no word's ids)
             int r_cu = 0;
             BPE_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&r_cu, k_enc_resolve, 256, 0));
             const unsigned long long ne = (unsigned long long)nblk * kPendBlock;
@@ -2392,6 +2396,23 @@ size_t encode_device(bpe_tokenizer& T, const uint8_t* d_text, size_t n, OutT* d_
             continue;
         }
         break;
+    }
+    if (drop) {   // every occurrence merges on its own: no word table, no resolve, no emit (dropout.hip)
+        if constexpr (std::is_same<OutT, uint32_t>::value) {
+            BPE_REQUIRE(want_pos, BPE_E_ARG, "encode with dropout needs the document starts");
+            S.chunk_next.reserve(n_chunks);
+            hipLaunchKernelGGL(k_enc_chunk_next, dim3(grid_for(n_chunks, 256)), dim3(256), 0, s, rec_n.p, rec_base.p,
+                               S.rec_pos.p, n_chunks, (unsigned long long)n, S.chunk_next.p);
+            BPE_HIP(hipGetLastError());
+            const DropTables DT{E.pm_key, E.pm_val, E.pm_mask, E.tok2vid, E.byte2tok, E.sp_bytes, E.sp_off, E.sp_len,
+                                E.sp_vid, E.n_sp};
+            const DropFront F{d_text, n, n_chunks, (size_t)kChunk, T.recs_cache.p, kRecKind3, kRecSpecial, kRecPayload29,
+                              S.rec_pos.p, rec_base.p, rec_n.p, S.chunk_next.p, S.cuts.p, S.chunk_cut0.p, S.cut_rec.p,
+                              &cuts, docs->starts, docs->n_docs, d_out, docs->d_out};
+            return dropout_emit(F, DT, *drop, S.drop, s);
+        } else {
+            BPE_REQUIRE(false, BPE_E_ARG, "encode with dropout writes uint32 ids");
+        }
     }
     DevBuf<uint32_t>&w_slot = S.w_slot, &w_len = S.w_len;
     DevBuf<unsigned long long>& w_off = S.w_off;
@@ -2656,6 +2677,29 @@ std::vector<unsigned long long> batch_cuts(const uint64_t* starts, size_t n_docs
     BPE_REQUIRE(n_docs == 0 || starts[n_docs - 1] <= n, BPE_E_ARG, "a document starts past the end of the text");
     return std::vector<unsigned long long>(starts, starts + n_docs);
 }
+
+}  // namespace
+
+hipStream_t tokenizer_stream(bpe_tokenizer* tok) { return tok->stream; }
+
+size_t encode_dropout_device(bpe_tokenizer* tok, const uint8_t* d_text, size_t n, const uint64_t* doc_starts,
+                             size_t n_docs, const DropParams& P, uint32_t* d_ids, unsigned long long* d_id_offsets,
+                             hipStream_t s) {
+    const std::vector<unsigned long long> cuts = batch_cuts(doc_starts, n_docs, n);
+    for (size_t i = 0; i < n_docs; ++i)
+        BPE_REQUIRE(((i + 1 < n_docs ? doc_starts[i + 1] : (uint64_t)n) - doc_starts[i]) >> 32 == 0, BPE_E_LIMIT,
+                    "a document of 2^32 bytes or more");
+    if (!s) s = tok->stream;
+    if (n == 0) {   // empty documents only: every offset is 0
+        BPE_HIP(hipMemsetAsync(d_id_offsets, 0, (n_docs + 1) * sizeof(uint64_t), s));
+        BPE_HIP(hipStreamSynchronize(s));
+        return 0;
+    }
+    const DocStarts docs{doc_starts, n_docs, d_id_offsets};
+    return encode_device(*tok, d_text, n, d_ids, s, cuts, &docs, nullptr, &P);
+}
+
+namespace {
 
 template <class F>
 int guarded_enc(F&& f) {

@@ -245,4 +245,57 @@ class WordAccumulator {
 
 bool timing_enabled();
 
+// ---------------------------------------------------------------- encode with dropout (dropout.hip)
+// BPE-dropout draws per occurrence, so nothing of the encoder behind its scan applies: encode.hip
+// runs its front (the segment table and the scan's kCuts, kPos instantiation) and hands the
+// records to dropout_emit, which merges every pre-token occurrence on its own.
+struct DropParams {
+    uint32_t thr;               // a candidate merge is skipped when its 24-bit draw is below thr
+    uint64_t seed, doc_base;    // document i of the call draws with doc_key = doc_base + i
+};
+struct DropTables {             // the tokenizer's tables (EncTables of encode.hip)
+    const unsigned long long* pm_key;  // ((a << 32) | b) + 1
+    const uint2* pm_val;               // (rank, product)
+    unsigned long long pm_mask;
+    const int64_t* tok2vid;            // internal token -> vocab id, -1 if absent
+    const uint32_t* byte2tok;
+    const uint8_t* sp_bytes;
+    const uint32_t* sp_off;
+    const uint32_t* sp_len;
+    const int64_t* sp_vid;
+    int n_sp;
+};
+struct DropFront {              // what the scan left, all device memory unless noted
+    const uint8_t* text;
+    size_t n, n_chunks, chunk;  // chunk: the bytes of one (kChunk)
+    uint32_t* recs;             // per record: its kind (only "special k" is read); reused for its id count
+    uint32_t kind_mask, kind_special, payload_mask;
+    const uint16_t* rec_pos;    // per record: its first byte, relative to its chunk
+    const unsigned long long* rec_base;   // per chunk: its run in recs / rec_pos
+    const uint32_t* rec_n;
+    const unsigned long long* chunk_next; // per chunk: the end of its last record
+    const unsigned long long* cuts;       // the document starts inside the text: sorted, distinct
+    const uint32_t* chunk_cut0;           // n_chunks + 1: the first cut at or after each chunk's first byte
+    const uint32_t* cut_rec;              // per cut: the record that starts there, inside its chunk's run
+    const std::vector<unsigned long long>* h_cuts;   // host: the cuts
+    const uint64_t* h_doc_starts;         // host
+    size_t n_docs;
+    uint32_t* d_ids;                      // out: >= n ids
+    unsigned long long* d_id_offsets;     // out: n_docs + 1
+};
+struct DropScratch {            // kept by the tokenizer between calls (grow-only)
+    DevBuf<uint32_t> pool, doc_cut;
+    DevBuf<unsigned long long> ctot, coff, cut_off, cut_doc, list;
+    DevBuf<unsigned> status;
+    DevBuf<uint8_t> tmp;
+};
+// returns the id count once d_ids and d_id_offsets are written
+size_t dropout_emit(const DropFront& F, const DropTables& E, const DropParams& P, DropScratch& S, hipStream_t s);
+// encode.hip: the front and dropout_emit for one batch (the document starts are checked as
+// bpe_tok_encode_batch checks them); s null: the tokenizer's own stream
+size_t encode_dropout_device(bpe_tokenizer* tok, const uint8_t* d_text, size_t n, const uint64_t* doc_starts,
+                             size_t n_docs, const DropParams& P, uint32_t* d_ids, unsigned long long* d_id_offsets,
+                             hipStream_t s);
+hipStream_t tokenizer_stream(bpe_tokenizer* tok);
+
 }  // namespace bpe
